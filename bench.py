@@ -8,7 +8,14 @@ enc 400 -> dec 100, vocab 50k, pointer-gen with coverage loss, bf16 compute (fp3
 weights + Adagrad accumulators), synthetic CNN/DM-shaped data, random-init weights.
 Weak scaling: the per-GPU batch is fixed, global batch = batch x N.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: set-up, W warmup steps, K timed steps, the
+result line (``ms_per_step`` = wall milliseconds per timed step).  ``--dump-outputs DIR``
+also writes what the timed path computes for the last timed step's batch from the seeded
+initial weights, reproducible from run to run (``dump_step`` below).  Everything under
+"Secondary" below and the per-phase timing steps (``phase_ms_max_over_ranks``,
+``ms_allreduce_exposed``) run with ``--full`` only.
 
 Multi-GPU: one process per GPU, torch.distributed over RCCL (backend "nccl"), gradients
 all-reduced in four buckets overlapped with the backward.  Either launch it with
@@ -24,13 +31,13 @@ replays), gradient all-reduce (RCCL), clip + Adagrad + weight repack (the optimi
 -- the complete optimizer step; only synthetic text generation/tokenisation is done ahead
 of time (like a prefetching loader).  The W warmup steps include the graph captures.
 
-Secondary (BASELINE config #4, ``beam4_summaries_per_sec``): after the training timing,
+Secondary, ``--full`` (BASELINE config #4, ``beam4_summaries_per_sec``): after the training timing,
 every rank decodes ``--decode-batches`` batches of 64 articles x beam 4 (hipGraph-captured
 device beam search, fresh random-init weights, encoder included, host backtracking
 included, tokenisation excluded); the value is the sum over ranks of completed summaries
 divided by the slowest rank's wall time.  ``--decode-batches 0`` skips it.
 
-Secondary (BASELINE config #5, ``config5_tokens_per_sec`` / ``config5_beam4_summaries_per_sec``):
+Secondary, ``--full`` (BASELINE config #5, ``config5_tokens_per_sec`` / ``config5_beam4_summaries_per_sec``):
 hidden 512, 2-layer encoder, enc 800, per-GPU batch sized for the GPU's HBM (the largest of
 2048 / 1024 / 512 whose captured step fits EVERY rank, agreed before any gradient collective;
 ``config5_peak_mem_gb`` reports the footprint), ``--config5-steps`` timed steps after two warm-up
@@ -73,12 +80,24 @@ def parse_args(argv=None):
     ap.add_argument("--decode-batches", type=int, default=10, help="timed beam-4 decode batches (0 = skip)")
     ap.add_argument("--decode-articles", type=int, default=64)
     ap.add_argument("--port", type=int, default=0, help="rendezvous port when launching ranks (0 = free port)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the per-phase timing steps, the beam-4 decode "
+                         "(--decode-batches) and BASELINE config #5 (--config5-steps).  Without it the run sets up, "
+                         "warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computes for the last timed step's batch, "
+                         "run once more from the seeded initial weights, as DIR/<name>.npy (float32): its loss "
+                         "scalars, the gradient norm, and a fixed seeded sample of the updated parameters and of "
+                         "the gradient")
     ap.add_argument("--config5-steps", type=int, default=10,
                     help="BASELINE config #5 (hidden 512, 2-layer encoder, enc 800, the HBM-sized per-GPU batch) timed "
                          "train steps + 4 beam-4 decode batches, reported as config5_* fields (0 = skip).  Every step "
                          "packs its batch on the host; the first one's pack (~40 ms at batch 2048) has no GPU work "
                          "to hide behind, so 10 steps rather than 5 keep that start-up cost from reading as ~7 ms/step")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _free_port() -> int:
@@ -163,6 +182,8 @@ def main(argv=None):
     batches = make_batches(hps, vocab, corpus, args.pool, pad_enc_to=args.enc)
     tr = GraphTrainer(hps, vocab.size(), B=B, T=args.enc, device=f"cuda:{dev_id}", info=info,
                       use_graph=not args.no_graph)
+    # --dump-outputs: the seeded initial weights and Adagrad accumulators, for dump_step
+    snap = (tr.params.flat.clone(), tr.params.accum.clone()) if args.dump_outputs else None
 
     for i in range(args.warmup):
         out = tr.step(batches[i % len(batches)])
@@ -183,23 +204,26 @@ def main(argv=None):
     vals = tr.check_finite(out)
     elapsed_max = D.all_reduce_scalar(elapsed, info, op="max", device=tr.device)
     elapsed_min = D.all_reduce_scalar(elapsed, info, op="min", device=tr.device)
-    # diagnostics, after the timed region: per-phase wall time of a few more steps (HIP events
-    # between the phase graphs; ms_allreduce = the all-reduce wait exposed after the backward)
-    tr.timing = True
+    if args.dump_outputs:
+        dump_step(args.dump_outputs, tr, snap, batches[(args.steps - 1) % len(batches)], info.is_chief)
     ph = {}
-    nph = 3
-    for i in range(nph):
-        tr.step(batches[i % len(batches)])
-        for k_, v_ in tr.phase_ms().items():
-            ph[k_] = ph.get(k_, 0.0) + v_ / nph
-    tr.timing = False
-    ph = {k_: round(D.all_reduce_scalar(v_, info, op="max", device=tr.device), 3) for k_, v_ in ph.items()}
+    if args.full:
+        # diagnostics, after the timed region: per-phase wall time of a few more steps (HIP events
+        # between the phase graphs; ms_allreduce = the all-reduce wait exposed after the backward)
+        tr.timing = True
+        nph = 3
+        for i in range(nph):
+            tr.step(batches[i % len(batches)])
+            for k_, v_ in tr.phase_ms().items():
+                ph[k_] = ph.get(k_, 0.0) + v_ / nph
+        tr.timing = False
+        ph = {k_: round(D.all_reduce_scalar(v_, info, op="max", device=tr.device), 3) for k_, v_ in ph.items()}
     tok_all = D.all_reduce_scalar(float(tokens), info, op="sum", device=tr.device)
     pad_all = D.all_reduce_scalar(float(padded), info, op="sum", device=tr.device)
     value = tok_all / elapsed_max
 
     dec = None
-    if args.decode_batches > 0:
+    if args.full and args.decode_batches > 0:
         dec = bench_decode(args, info, D, torch, dev_id)
     peak_gb = torch.cuda.max_memory_allocated() / 2 ** 30
     eng_flags = {"persistent_lstm": bool(tr.engine.persistent_lstm), "proj_attn": bool(tr.engine.proj_attn),
@@ -211,7 +235,7 @@ def main(argv=None):
     # which activation GEMMs ran on the hand-written kernel (fixed table, not per-run timing)
     eng_flags["gemm_dispatch"] = _pg.gemm_bt_stats()
     c5 = None
-    if args.config5_steps > 0 and args.hidden != 512:
+    if args.full and args.config5_steps > 0 and args.hidden != 512:
         del tr, batches
         torch.cuda.empty_cache()
         # no rank-local OOM handling here: bench_config5 agrees on a batch that fits every rank
@@ -244,8 +268,7 @@ def main(argv=None):
                 "grad_allreduce": ("bf16" if args.grad_compress == "bf16" else "fp32") if info.enabled else "none",
                 "padded_tokens_per_sec": round(pad_all / elapsed_max, 1),
                 "ms_per_step_rank_min": round(1000.0 * elapsed_min / args.steps, 3),
-                "ms_allreduce_exposed": ph.get("ms_allreduce"),
-                "phase_ms_max_over_ranks": ph,
+                **({"ms_allreduce_exposed": ph.get("ms_allreduce"), "phase_ms_max_over_ranks": ph} if args.full else {}),
                 "loss": round(vals.get("total_loss", float("nan")), 4),
                 "graph": not args.no_graph,
                 # projected-context attention and skipped dead decoder steps (loss and gradients
@@ -263,6 +286,44 @@ def main(argv=None):
     if info.enabled:
         torch.distributed.destroy_process_group()
     return 0
+
+
+DUMP_SAMPLE = 1 << 20  # elements kept of each flat buffer (4 MiB as float32)
+
+
+def dump_step(path, tr, snap, batch, write):
+    """``--dump-outputs``: what the timed path computes for the last timed step's batch, one float32
+    ``.npy`` each -- the loss scalars ``step`` returns, the clipped-gradient norm, and the same
+    seeded sample of positions (sorted, identical from run to run) of the updated fp32 parameters
+    and of the all-reduced gradient.
+
+    The step is run once more, outside the timed region, from the seeded initial weights and
+    Adagrad accumulators (``snap``) instead of from the state the timed steps left.  That state is
+    no function of the arguments alone: the step sums gradients with fp32 atomics, so two runs
+    differ in the last bits after one step, and bf16 activations with Adagrad's early large updates
+    amplify that step by step (two runs of one build at batch 256: gradient sample 4e-8 apart in
+    relative norm after 1 step, 1.6e-4 after 5, of order 1 after 100; parameters 4e-3 after 100).
+    From the fixed state the same batches, weights and code path give the same arrays up to that
+    last-bit summation order, so two builds can be compared file by file at any --steps.
+    Every rank runs the step (its collectives); only ``write`` ranks write."""
+    import numpy as np
+    import torch
+    tr.params.flat.copy_(snap[0])
+    tr.params.accum.copy_(snap[1])
+    tr.engine.pack()  # the bf16 weight copies the kernels read
+    out = tr.step(batch)
+    vals = tr.check_finite(out)
+    if not write:
+        return
+    os.makedirs(path, exist_ok=True)
+    for k in out:
+        np.save(os.path.join(path, f"{k}.npy"), np.asarray([vals[k]], dtype=np.float32))
+    np.save(os.path.join(path, "global_norm.npy"), np.asarray([vals["global_norm"]], dtype=np.float32))
+    n = tr.params.flat.numel()
+    idx = np.sort(np.random.RandomState(0).randint(0, n, size=min(n, DUMP_SAMPLE)))
+    idx = torch.from_numpy(idx).to(tr.params.flat.device)
+    np.save(os.path.join(path, "params_sample.npy"), tr.params.flat.detach().float()[idx].cpu().numpy())
+    np.save(os.path.join(path, "grad_sample.npy"), tr.params.grad.detach().float()[idx].cpu().numpy())
 
 
 AUTO_BATCHES = (2048, 1024, 512, 256, 128)

@@ -21,10 +21,10 @@ cfg5)
   timeout -k 10 300 python -u -m pytest -x -v --timeout 200 --timeout-method thread tests/test_gpu_attention_ops.py \
     tests/test_gpu_model.py -k "attn or attention" > $OUT/pytest.log 2>&1
   rc=$?; tail -3 $OUT/pytest.log; [ $rc -eq 0 ] || exit $rc
-  timeout -k 10 300 python bench.py $CFG5 > $OUT/cfg5.log 2>&1 || { tail -20 $OUT/cfg5.log; exit 1; }
+  timeout -k 10 300 python bench.py --full $CFG5 > $OUT/cfg5.log 2>&1 || { tail -20 $OUT/cfg5.log; exit 1; }
   tail -1 $OUT/cfg5.log ;;
 cfg5prof)
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py $CFG5 \
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --full $CFG5 \
     > $OUT/prof.log 2>&1 || { tail -20 $OUT/prof.log; exit 1; }
   python scripts/kstats.py $OUT/prof/run_kernel_stats.csv 4 40 > $OUT/kstats.txt; tail -1 $OUT/prof.log ;;
 decode)
@@ -43,11 +43,11 @@ train)
   i=0
   for v in ${AB_VALUES:-1 0 1 0}; do
     i=$((i+1))
-    env $AB_ENV=$v timeout -k 10 300 python bench.py --decode-batches 0 --steps 40 --warmup 5 > $OUT/b$i.log 2>&1 \
+    env $AB_ENV=$v timeout -k 10 300 python bench.py --full --decode-batches 0 --steps 40 --warmup 5 > $OUT/b$i.log 2>&1 \
       || { tail -20 $OUT/b$i.log; exit 1; }
     j $OUT/b$i.log "B=256 $AB_ENV=$v"
     if [ -n "$AB_CFG5" ]; then
-      env $AB_ENV=$v timeout -k 10 300 python bench.py --hidden 512 --layers 2 --enc 800 --batch 512 --steps 4 \
+      env $AB_ENV=$v timeout -k 10 300 python bench.py --full --hidden 512 --layers 2 --enc 800 --batch 512 --steps 4 \
         --warmup 1 --decode-batches 0 > $OUT/c$i.log 2>&1 || { tail -20 $OUT/c$i.log; exit 1; }
       j $OUT/c$i.log "cfg5 B=512 $AB_ENV=$v"
     fi

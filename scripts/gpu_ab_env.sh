@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 i=0
 for v in $VARIANTS; do
   i=$((i+1)); e=""; [ "$v" != "-" ] && e="${v//:/ }"
-  timeout -k 10 400 env $e python bench.py ${BENCH_ARGS} > $OUT/v$i.log 2>&1 || { tail -20 $OUT/v$i.log; exit 1; }
+  timeout -k 10 400 env $e python bench.py --full ${BENCH_ARGS} > $OUT/v$i.log 2>&1 || { tail -20 $OUT/v$i.log; exit 1; }
   echo "[$v] $(tail -1 $OUT/v$i.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["ms_per_step"], d["value"], d.get("beam4_summaries_per_sec"))')"
 done
 echo done

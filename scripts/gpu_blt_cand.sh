@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/${OUTD:-bltc}; mkdir -p $OUT
 export TMPDIR=/tmp
 step() { local n=$1; shift; echo "== $n"; timeout -k 10 ${T:-300} "$@" > $OUT/$n.log 2>&1; local rc=$?; grep -o '"ms_per_step": [0-9.]*\|"phase_ms_max_over_ranks": {[^}]*}\|"config5_ms_per_step": [0-9.]*' $OUT/$n.log | tr '\n' ' '; echo; return $rc; }
-B="python -u bench.py --decode-batches 0"
+B="python -u bench.py --full --decode-batches 0"
 T=400 step c24 env TSAMD_BLT_CANDIDATES=24 $B &&
 T=400 step c64 env TSAMD_BLT_CANDIDATES=64 $B &&
 T=400 step c8 env TSAMD_BLT_CANDIDATES=8 $B &&

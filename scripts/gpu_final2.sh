@@ -22,6 +22,6 @@ timeout -k 10 300 python tools/cli_throughput.py --root /tmp/tsamd_cli --example
 tail -1 $OUT/cli_host.log
 timeout -k 10 400 python tools/stream_latency.py --requests 60 --interval-ms 50 --waits 0,20 > $OUT/lat.log 2>&1 || { tail -20 $OUT/lat.log; exit 1; }
 grep '^{' $OUT/lat.log
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof5 -o run --output-format csv -- python3 bench.py --hidden 512 --layers 2 --enc 800 --batch 512 --steps 2 --warmup 1 --decode-batches 0 > $OUT/prof5.log 2>&1 || { tail -20 $OUT/prof5.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof5 -o run --output-format csv -- python3 bench.py --full --hidden 512 --layers 2 --enc 800 --batch 512 --steps 2 --warmup 1 --decode-batches 0 > $OUT/prof5.log 2>&1 || { tail -20 $OUT/prof5.log; exit 1; }
 python scripts/kstats.py $OUT/prof5/run_kernel_stats.csv 5 30 > $OUT/cfg5_kstats.txt
 echo done

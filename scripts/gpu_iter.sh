@@ -11,7 +11,7 @@ fi
 i=0
 for a in "" $BENCH_VARIANTS; do
   i=$((i+1))
-  timeout -k 10 300 env $a python bench.py ${BENCH_ARGS} > $OUT/bench$i.log 2>&1 || { tail -20 $OUT/bench$i.log; exit 1; }
+  timeout -k 10 300 env $a python bench.py --full ${BENCH_ARGS} > $OUT/bench$i.log 2>&1 || { tail -20 $OUT/bench$i.log; exit 1; }
   echo "[$a] $(tail -1 $OUT/bench$i.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["ms_per_step"], d["value"], d.get("beam4_summaries_per_sec"), d.get("beam4_ms_per_batch"))')"
 done
 echo done

@@ -8,5 +8,5 @@ step() { local n=$1; shift; echo "== $n"; timeout -k 10 ${T:-300} "$@" > $OUT/$n
 step tests python -u -m pytest tests/test_gpu_decode.py tests/test_gpu_model.py -q -x --timeout 300 --timeout-method thread &&
 step dec1 python -u bench_decode.py --batches 10 &&
 step dec2 python -u bench_decode.py --batches 10 &&
-T=600 step bench1 python -u bench.py --decode-batches 4 &&
-T=600 step bench2 python -u bench.py --decode-batches 4
+T=600 step bench1 python -u bench.py --full --decode-batches 4 &&
+T=600 step bench2 python -u bench.py --full --decode-batches 4

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 step() { local n=$1; shift; echo "== $n"; timeout -k 10 ${T:-300} "$@" > $OUT/$n.log 2>&1; local rc=$?; tail -${TL:-3} $OUT/$n.log; return $rc; }
 step prod python -u -m pytest tests/test_gpu_production.py tests/test_gpu_dist.py -x -q --timeout 200 --timeout-method thread &&
 step vtest python -u -m pytest tests/test_gpu_decode.py -x -q --timeout 100 --timeout-method thread -k "vocab_topk or fused_decode" &&
-step bench python -u bench.py --config5-steps 0 &&
+step bench python -u bench.py --full --config5-steps 0 &&
 T=400 step vprof rocprofv3 --kernel-trace --stats -d $OUT/v -o run --output-format csv -- python3 tools/vocab_micro.py &&
 python scripts/kstats.py $OUT/v/run_kernel_stats.csv 1 4 &&
 step dec_fused python -u bench_decode.py --batches 10 &&

@@ -14,4 +14,4 @@ step lstm python -u -m pytest tests/test_gpu_lstm.py -x -q --timeout 100 --timeo
 step micro32 python -u tools/lstm_micro.py 512:512:800 512:1024:800 512:2048:800 &&
 TSAMD_LSTM_BWD32=0 step micro16 python -u tools/lstm_micro.py 512:512:800 512:1024:800 512:2048:800 &&
 step cfg5test python -u -m pytest tests/test_gpu_production.py -x -q --timeout 200 --timeout-method thread -k config5 &&
-T=600 step bench python -u bench.py --steps 10 --warmup 3
+T=600 step bench python -u bench.py --full --steps 10 --warmup 3

@@ -11,4 +11,4 @@ T=900 step tier python -u -m pytest tests -m gpu -q --timeout 300 --timeout-meth
 [ $rc -le 1 ] &&
 step ph256 python -u tools/phase_micro.py &&
 step ph5 python -u tools/phase_micro.py --batch 1024 --hidden 512 --enc 800 --layers 2 --iters 3 &&
-T=600 step bench python -u bench.py
+T=600 step bench python -u bench.py --full

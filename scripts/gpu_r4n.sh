@@ -12,4 +12,4 @@ T=900 step tier python -u -m pytest tests -m gpu -q -x --timeout 300 --timeout-m
 step dec python -u bench_decode.py --batches 10 &&
 step thr python -u tools/stream_throughput.py --only transform --out $OUT/stream_thr.jsonl &&
 step lat python -u tools/stream_latency.py --requests 60 --waits 0 &&
-step bench python -u bench.py
+step bench python -u bench.py --full

@@ -17,8 +17,8 @@ for v in 1 0; do
 done
 TSAMD_VS_ART=0 TL=1 step dec0 python -u bench_decode.py --batches 10 || exit 1
 TL=1 step dec1 python -u bench_decode.py --batches 10 || exit 1
-T=600 TL=1 step bench python -u bench.py || exit 1
-step trace rocprofv3 --kernel-trace -d $OUT/tr -o run --output-format csv -- python3 bench.py --steps 2 --warmup 1 --decode-batches 0 --config5-steps 0 || exit 1
+T=600 TL=1 step bench python -u bench.py --full || exit 1
+step trace rocprofv3 --kernel-trace -d $OUT/tr -o run --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --decode-batches 0 --config5-steps 0 || exit 1
 python scripts/kwin.py $OUT/tr/run_kernel_trace.csv 1 40 > $OUT/kwin_b256.txt
 python scripts/loop_tl.py $OUT/tr/run_kernel_trace.csv attn_bwd_rowp 60 30 > $OUT/tl_bwd.txt
 python scripts/loop_tl.py $OUT/tr/run_kernel_trace.csv attn_fwd_rowp 60 30 > $OUT/tl_fwd.txt

@@ -11,9 +11,9 @@ step kt python -u -m pytest tests/test_gpu_gemm.py tests/test_gpu_lstm.py -q -x 
 T=600 step orc python -u -m pytest tests/test_gpu_production.py -q -x --timeout 300 --timeout-method thread -k "config5_shape or bench_shape" || exit 1
 step m1 python -u tools/lstm_micro.py 512:1024:800 512:2048:800 512:768:800 || exit 1
 TSAMD_LSTM_FWD64=0 step m0 python -u tools/lstm_micro.py 512:1024:800 512:2048:800 512:768:800 || exit 1
-T=500 TL=1 step c11 python -u bench.py --steps 1 --warmup 1 --decode-batches 0 --config5-steps 3 || exit 1
-TSAMD_LSTM_FWD64=0 T=500 TL=1 step c01 python -u bench.py --steps 1 --warmup 1 --decode-batches 0 --config5-steps 3 || exit 1
-TSAMD_DX_MERGE=0 T=500 TL=1 step c10 python -u bench.py --steps 1 --warmup 1 --decode-batches 0 --config5-steps 3 || exit 1
-T=400 TL=1 step b1 python -u bench.py --steps 20 --warmup 3 --decode-batches 0 --config5-steps 0 || exit 1
-TSAMD_DX_MERGE=0 T=400 TL=1 step b0 python -u bench.py --steps 20 --warmup 3 --decode-batches 0 --config5-steps 0 || exit 1
+T=500 TL=1 step c11 python -u bench.py --full --steps 1 --warmup 1 --decode-batches 0 --config5-steps 3 || exit 1
+TSAMD_LSTM_FWD64=0 T=500 TL=1 step c01 python -u bench.py --full --steps 1 --warmup 1 --decode-batches 0 --config5-steps 3 || exit 1
+TSAMD_DX_MERGE=0 T=500 TL=1 step c10 python -u bench.py --full --steps 1 --warmup 1 --decode-batches 0 --config5-steps 3 || exit 1
+T=400 TL=1 step b1 python -u bench.py --full --steps 20 --warmup 3 --decode-batches 0 --config5-steps 0 || exit 1
+TSAMD_DX_MERGE=0 T=400 TL=1 step b0 python -u bench.py --full --steps 20 --warmup 3 --decode-batches 0 --config5-steps 0 || exit 1
 echo done

@@ -10,6 +10,6 @@ TSAMD_GEMM_V=5 step gemmt5 python -u -m pytest tests/test_gpu_gemm.py -q -x --ti
 TL=10 step gemm3 python -u tools/gemm_micro.py || exit 1
 TSAMD_GEMM_V=5 TL=10 step gemm5 python -u tools/gemm_micro.py || exit 1
 TSAMD_GEMM_V=5 T=600 step orc5 python -u -m pytest tests/test_gpu_production.py -q -x --timeout 300 --timeout-method thread -k "config5_shape or bench_shape" || exit 1
-TSAMD_GEMM_V=5 T=500 TL=1 step c5 python -u bench.py --steps 20 --warmup 3 --decode-batches 0 --config5-steps 3 || exit 1
-T=500 TL=1 step c3 python -u bench.py --steps 20 --warmup 3 --decode-batches 0 --config5-steps 3 || exit 1
+TSAMD_GEMM_V=5 T=500 TL=1 step c5 python -u bench.py --full --steps 20 --warmup 3 --decode-batches 0 --config5-steps 3 || exit 1
+T=500 TL=1 step c3 python -u bench.py --full --steps 20 --warmup 3 --decode-batches 0 --config5-steps 3 || exit 1
 echo done

@@ -6,9 +6,9 @@ cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/${OUTD:-r6n}; mkdir -p $OUT
 export TMPDIR=/tmp
 timeout -k 10 900 python -u -m pytest tests/test_gpu_production.py tests/test_gpu_model.py -m gpu -x -v --timeout 300 --timeout-method thread > $OUT/pytest.log 2>&1; rc=$?; tail -3 $OUT/pytest.log; [ $rc -eq 0 ] || exit $rc
-s=$(date +%s); timeout -k 10 600 python bench.py > $OUT/bench_table.log 2>&1 || { tail -20 $OUT/bench_table.log; exit 1; }
+s=$(date +%s); timeout -k 10 600 python bench.py --full > $OUT/bench_table.log 2>&1 || { tail -20 $OUT/bench_table.log; exit 1; }
 echo "bench wall $(( $(date +%s) - s )) s"; tail -1 $OUT/bench_table.log > $OUT/bench_table.json
-TSAMD_GEMM_BT=auto timeout -k 10 600 python bench.py > $OUT/bench_auto.log 2>&1 || { tail -20 $OUT/bench_auto.log; exit 1; }
+TSAMD_GEMM_BT=auto timeout -k 10 600 python bench.py --full > $OUT/bench_auto.log 2>&1 || { tail -20 $OUT/bench_auto.log; exit 1; }
 tail -1 $OUT/bench_auto.log > $OUT/bench_auto.json
 python - <<'PY'
 import json,os

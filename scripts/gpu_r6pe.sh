@@ -10,7 +10,7 @@ for g in 4 2 1 4 2 1; do
   python -c "import json;r=json.loads(open('$OUT/dec_g$g.log').read().strip().splitlines()[-1]);print('group $g bench_decode', r['value'], r.get('ms_per_batch'))"
 done
 for g in 4 1; do
-  TSAMD_DEC_GROUP_ENC=$g timeout -k 10 300 python bench.py --steps 3 --warmup 1 --config5-steps 0 > $OUT/bench_g$g.log 2>&1 || exit 1
+  TSAMD_DEC_GROUP_ENC=$g timeout -k 10 300 python bench.py --full --steps 3 --warmup 1 --config5-steps 0 > $OUT/bench_g$g.log 2>&1 || exit 1
   python -c "import json;r=json.loads(open('$OUT/bench_g$g.log').read().strip().splitlines()[-1]);print('group $g bench.py', r.get('beam4_summaries_per_sec'))"
 done
 echo done

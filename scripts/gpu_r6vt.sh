@@ -13,7 +13,7 @@ TSAMD_VT_NI=2 timeout -k 10 600 python -u -m pytest -x -q --timeout 300 --timeou
   -k "fused_vocab_head" > $OUT/tests.log 2>&1 || { tail -30 $OUT/tests.log; exit 1; }
 tail -2 $OUT/tests.log
 for ni in 0 2 0 2; do
-  TSAMD_VT_NI=$ni timeout -k 10 300 python bench.py --steps 20 --warmup 5 --decode-batches 0 --config5-steps 0 > $OUT/b_ni$ni.log 2>&1 || { echo "ni=$ni failed"; tail -5 $OUT/b_ni$ni.log; exit 1; }
+  TSAMD_VT_NI=$ni timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --decode-batches 0 --config5-steps 0 > $OUT/b_ni$ni.log 2>&1 || { echo "ni=$ni failed"; tail -5 $OUT/b_ni$ni.log; exit 1; }
   python -c "import json;r=json.loads(open('$OUT/b_ni$ni.log').read().strip().splitlines()[-1]);print('ni=$ni', r['ms_per_step'], r.get('phase_ms_max_over_ranks'))"
 done
 echo done

@@ -4,7 +4,7 @@ runs alone (nothing else on the GPU) and the time it shares the GPU, ms per step
 Idle intervals (no kernel running) are also grouped by (kernel that ended last -> kernel that
 starts next): the bubbles of the step by where they sit.
 usage: kgaps.py <kernel_trace.csv> <N> [top, default 25] [marker substring, default adagrad_kernel] [skip]
-(skip: leave out the last `skip` steps, e.g. bench.py's phase-timed diagnostic steps)"""
+(skip: leave out the last `skip` steps, e.g. the phase-timed diagnostic steps of bench.py --full)"""
 import csv
 import sys
 

@@ -2,7 +2,7 @@
 dispatches after the (N+1)-th last optimizer kernel up to the last one), so one-off work before
 them (graph capture warm-up, blt_mm's candidate timing) is left out.
 usage: kwin.py <kernel_trace.csv> <N> [top, default 40] [marker substring, default adagrad_kernel] [skip]
-(skip: leave out the last `skip` steps, e.g. bench.py's phase-timed diagnostic steps)"""
+(skip: leave out the last `skip` steps, e.g. the phase-timed diagnostic steps of bench.py --full)"""
 import csv
 import sys
 

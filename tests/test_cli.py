@@ -20,13 +20,20 @@ def ds(tmp_path):
     return tmp_path, d, vp
 
 
+def _hide_gpu(monkeypatch):
+    """The CPU oracle backend, also on a machine that has a GPU: the CLI picks its trainer by
+    ``is_available()`` and its input pipeline by ``device_count()``."""
+    monkeypatch.setattr("torch.cuda.is_available", lambda: False)
+    monkeypatch.setattr("torch.cuda.device_count", lambda: 0)
+
+
 def _flags(tmp, d, vp, *extra, split="train"):
     return [f"--data_path={d}/{split}_*", f"--vocab_path={vp}", f"--log_root={tmp}/log", "--exp_name=exp",
             *TINY_FLAGS, *extra]
 
 
 def test_train_resume_eval_decode(ds, monkeypatch):
-    monkeypatch.setattr("torch.cuda.is_available", lambda: False)
+    _hide_gpu(monkeypatch)
     tmp, d, vp = ds
     assert cli.main(_flags(tmp, d, vp, "--mode=train", "--num_steps=3")) == 0
     train_dir = f"{tmp}/log/exp/train"
@@ -63,7 +70,7 @@ def test_train_resume_eval_decode(ds, monkeypatch):
 
 
 def test_inference_raw_text_and_conversions(ds, monkeypatch):
-    monkeypatch.setattr("torch.cuda.is_available", lambda: False)
+    _hide_gpu(monkeypatch)
     tmp, d, vp = ds
     assert cli.main(_flags(tmp, d, vp, "--mode=train", "--num_steps=1", "--coverage=0")) == 0
     raw = tmp / "raw"
@@ -84,7 +91,7 @@ def test_inference_raw_text_and_conversions(ds, monkeypatch):
 
 
 def test_restore_best_model(ds, monkeypatch):
-    monkeypatch.setattr("torch.cuda.is_available", lambda: False)
+    _hide_gpu(monkeypatch)
     tmp, d, vp = ds
     assert cli.main(_flags(tmp, d, vp, "--mode=train", "--num_steps=2")) == 0
     from textsummarization_on_flink_amd.config import parse_flags
@@ -97,7 +104,7 @@ def test_restore_best_model(ds, monkeypatch):
 
 
 def test_nan_fault_injection_stops_training(ds, monkeypatch):
-    monkeypatch.setattr("torch.cuda.is_available", lambda: False)
+    _hide_gpu(monkeypatch)
     tmp, d, vp = ds
     with pytest.raises(NonFiniteLossError, match="Loss is not finite"):
         cli.main(_flags(tmp, d, vp, "--mode=train", "--num_steps=5", "--fault_nan_step=2"))
@@ -118,7 +125,7 @@ def test_non_train_mode_requires_logdir(ds):
 def test_debug_watch_names_nonfinite_tensors(ds, monkeypatch, caplog):
     """--debug (tfdbg has_inf_or_nan): the step whose gradients carry NaN stops training and
     the report names the offending tensors."""
-    monkeypatch.setattr("torch.cuda.is_available", lambda: False)
+    _hide_gpu(monkeypatch)
     tmp, d, vp = ds
     with pytest.raises(NonFiniteLossError, match="has_inf_or_nan"):
         cli.main(_flags(tmp, d, vp, "--mode=train", "--num_steps=5", "--fault_nan_step=1", "--debug=1"))
@@ -127,7 +134,7 @@ def test_debug_watch_names_nonfinite_tensors(ds, monkeypatch, caplog):
 
 
 def test_log_file_rotating_handler(ds, monkeypatch):
-    monkeypatch.setattr("torch.cuda.is_available", lambda: False)
+    _hide_gpu(monkeypatch)
     tmp, d, vp = ds
     log_file = f"{tmp}/logs/run.log"
     cli.main(_flags(tmp, d, vp, "--mode=train", "--num_steps=1", f"--log_file={log_file}"))

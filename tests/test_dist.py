@@ -152,7 +152,8 @@ def test_dead_rank_surfaces_and_training_restarts_from_latest(tmp_path):
     # restart from latest on a fresh single-process launch
     from textsummarization_on_flink_amd import cli
     import unittest.mock as um
-    with um.patch("torch.cuda.is_available", lambda: False):
+    # no GPU for the CLI, also where the machine has one (it sizes its input pipeline by device_count)
+    with um.patch("torch.cuda.is_available", lambda: False), um.patch("torch.cuda.device_count", lambda: 0):
         assert cli.main([f for f in flags if not f.startswith("--fault_kill")] + ["--num_steps=2"]) == 0
     assert ckpt.latest_checkpoint(f"{tmp_path}/log/exp/train").endswith("model.ckpt-3")
 

@@ -121,7 +121,7 @@ def test_bench_launches_its_own_ranks():
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--backend", "gloo",
                         "--steps", "2", "--warmup", "1", "--batch", "16", "--enc", "64", "--dec", "8",
                         "--vocab", "2000", "--hidden", "64", "--emb", "64", "--pool", "2",
-                        "--decode-batches", "2", "--decode-articles", "8", "--config5-steps", "0"],
+                        "--full", "--decode-batches", "2", "--decode-articles", "8", "--config5-steps", "0"],
                        capture_output=True, text=True, timeout=110, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
