@@ -215,6 +215,57 @@ void attn_bwd_row(const Tensor& E, const Tensor& F, const Tensor& s, const Tenso
 // projected-context row attention (training): G = enc_out . W_in[E:] ([B, T, 128]) replaces E in
 // the recurrence; the kernels output / consume g_t = sum_i a_i G_i and dx_{t+1} (attention_row.hip)
 bool attn_rowp_ok(int64_t A, int64_t T, int64_t EG) { return attn_rowp_supported((int)A, (int)T, (int)EG); }
+// persistent decoder forward loop: all D steps of cell -> s-projection -> attn_fwd_rowp in one launch
+// (decoder_persistent.hip).  The caller zeroes xbuf before every launch.
+bool dec_persistent_ok_op(int64_t H, int64_t E, int64_t A, int64_t B, int64_t T) {
+  return dec_persistent_shape_ok((int)H, (int)E, (int)A, (int)B, (int)T);
+}
+int64_t dec_persistent_grid_op(int64_t B) { return dec_persistent_grid((int)B); }
+int64_t dec_persistent_capacity_op() { return dec_persistent_capacity(); }
+int64_t dec_persistent_xbuf_op(int64_t B) { return (int64_t)dec_persistent_xbuf_elems((int)B); }
+void dec_fwd_persistent(const Tensor& XG, const Tensor& KcT, const Tensor& WsT, const Tensor& bs, const Tensor& Cst,
+                        const Tensor& Cb, const Tensor& Hb, const Tensor& ACT, const Tensor& S, const Tensor& F,
+                        const Tensor& G, const Tensor& v, const OT& wc, const OT& COV, const Tensor& lens,
+                        const Tensor& ATT, const Tensor& ATTb, const OT& covloss, const Tensor& GV, const Tensor& GVb,
+                        const OT& dlen, const Tensor& xbuf, const Tensor& err, int64_t B, int64_t T, int64_t D,
+                        int64_t H, int64_t E, int64_t A) {
+  TORCH_CHECK(dec_persistent_shape_ok((int)H, (int)E, (int)A, (int)B, (int)T) && D >= 1,
+              "dec_fwd_persistent: unsupported shape");
+  const int64_t grid = dec_persistent_grid((int)B);
+  TORCH_CHECK(grid > 0 && grid <= dec_persistent_capacity(),
+              "dec_fwd_persistent: the grid would not be co-resident on this device");
+  chk(XG, F32, "XG"); numel_eq(XG, D * B * 4 * H, "XG");
+  chk(KcT, BF, "KcT"); numel_eq(KcT, 4 * H * (E + H), "KcT");
+  chk(WsT, BF, "WsT"); numel_eq(WsT, A * 2 * H, "WsT");
+  chk(bs, F32, "bs"); numel_eq(bs, A, "bs");
+  chk(Cst, F32, "Cst"); numel_eq(Cst, (D + 1) * B * H, "Cst");
+  chk(Cb, BF, "Cb"); numel_eq(Cb, (D + 1) * B * H, "Cb");
+  chk(Hb, BF, "Hb"); numel_eq(Hb, (D + 1) * B * H, "Hb");
+  chk(ACT, F32, "ACT"); numel_eq(ACT, D * B * 4 * H, "ACT");
+  chk(S, F32, "S"); numel_eq(S, D * B * A, "S");
+  chk(F, BF, "F"); numel_eq(F, B * T * A, "F");
+  chk(G, BF, "G"); numel_eq(G, B * T * E, "G");
+  chk(v, F32, "v"); numel_eq(v, A, "v");
+  chko(wc, F32, A, "wc");
+  chko(COV, F32, (D + 1) * B * T, "COV");
+  chk(lens, I32, "lens"); numel_eq(lens, B, "lens");
+  chk(ATT, F32, "ATT"); numel_eq(ATT, D * B * T, "ATT");
+  chk(ATTb, BF, "ATTb"); numel_eq(ATTb, D * B * T, "ATTb");
+  chko(covloss, F32, D * B, "covloss");
+  TORCH_CHECK((PO<float>(COV) != nullptr) == (PO<float>(covloss) != nullptr), "COV and covloss go together");
+  chk(GV, F32, "GV"); numel_eq(GV, D * B * E, "GV");
+  chk(GVb, BF, "GVb"); numel_eq(GVb, D * B * E, "GVb");
+  chko(dlen, I32, B, "dlen");
+  chk(xbuf, at::kLong, "xbuf"); numel_eq(xbuf, (int64_t)dec_persistent_xbuf_elems((int)B), "xbuf");
+  chk(err, I32, "err");
+  launch_dec_fwd_persistent(P<float>(XG), P<bf16>(KcT), P<bf16>(WsT), P<float>(bs), P<float>(Cst), P<bf16>(Cb),
+                            P<bf16>(Hb), P<float>(ACT), P<float>(S), P<bf16>(F), P<bf16>(G), P<float>(v),
+                            PO<float>(wc), PO<float>(COV), P<int>(lens), P<float>(ATT), P<bf16>(ATTb),
+                            PO<float>(covloss), P<float>(GV), P<bf16>(GVb), PO<int>(dlen),
+                            (unsigned long long*)xbuf.data_ptr(), (unsigned*)err.data_ptr(), (int)B, (int)T, (int)D,
+                            stream());
+}
+
 void attn_fwd_rowp(const Tensor& F, const Tensor& G, const Tensor& s, const Tensor& v, const OT& wc, const OT& cov,
                    const Tensor& lens, const Tensor& a_out, const OT& cov_out, const OT& covloss, const Tensor& gx,
                    const Tensor& gx_bf, int64_t B, int64_t T, int64_t A, const OT& dlen, int64_t step,
@@ -1172,6 +1223,11 @@ TORCH_LIBRARY(tsamd, m) {
   m.def("attn_bwd_row", &attn_bwd_row);
   m.def("attn_rowp_ok", &attn_rowp_ok);
   m.def("attn_fwd_rowp", &attn_fwd_rowp);
+  m.def("dec_persistent_ok", &dec_persistent_ok_op);
+  m.def("dec_persistent_grid", &dec_persistent_grid_op);
+  m.def("dec_persistent_capacity", &dec_persistent_capacity_op);
+  m.def("dec_persistent_xbuf", &dec_persistent_xbuf_op);
+  m.def("dec_fwd_persistent", &dec_fwd_persistent);
   m.def("attn_bwd_rowp", &attn_bwd_rowp);
   m.def("attn_bwd_feat", &attn_bwd_feat);
   m.def("attn_chunks", &attn_chunks);

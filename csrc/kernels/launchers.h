@@ -58,6 +58,16 @@ void launch_beam_sproj_xmerge(const bf16* cb, const bf16* hb, const bf16* WsT, c
                               hipStream_t st);
 void launch_dec_sproj(const bf16* cb, const bf16* hb, const bf16* WsT, const float* bs, float* s_out, int B, int H,
                       int A, const int* dlen, int step, hipStream_t st);
+// persistent decoder forward loop (decoder_persistent.hip): all D steps in one launch
+bool dec_persistent_shape_ok(int H, int E, int A, int B, int T);
+int dec_persistent_grid(int B);
+int dec_persistent_capacity();
+size_t dec_persistent_xbuf_elems(int B);
+void launch_dec_fwd_persistent(const float* XG, const bf16* KcT, const bf16* WsT, const float* bs, float* Cst, bf16* Cb,
+                               bf16* Hb, float* ACT, float* S, const bf16* F, const bf16* G, const float* v,
+                               const float* wc, float* COV, const int* lens, float* ATT, bf16* ATTb, float* covloss,
+                               float* GV, bf16* GVb, const int* dlen, unsigned long long* xbuf, unsigned* err, int B,
+                               int T, int D, hipStream_t st);
 void launch_dec_bwd_cell(const float* ds, const bf16* Ws, const float* dC_dir, const float* dH_dir,
                          const float* dh_rec, float* dc_carry, const float* act, const float* c_now,
                          const float* c_prev, bf16* dz, int B, int H, int A, const int* dlen, int step,

@@ -24,60 +24,12 @@
 // Layouts are those of lstm.hip (step frame; gx and acts [2][T][B][H][4 gates], hs/cs [2][T+1][B][H],
 // out [B][T][2H], dz [2][T][B][4H]), so the two implementations are interchangeable.
 #include "common.h"
+#include "handoff.h"
 #include <stdlib.h>
 
-typedef __attribute__((address_space(1))) unsigned long long gu64;
-typedef __attribute__((address_space(1))) unsigned int gu32;
-#define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+using namespace handoff;
 
 namespace {
-
-constexpr unsigned kSpinLimit = 1u << 21;  // x s_sleep(1): ~0.1-1 s before giving up
-
-__device__ __forceinline__ unsigned pack_bf2(float lo, float hi) {
-  const unsigned a = __builtin_bit_cast(unsigned short, f2bf(lo));
-  const unsigned b = __builtin_bit_cast(unsigned short, f2bf(hi));
-  return a | (b << 16);
-}
-
-__device__ __forceinline__ void store_granule(gu64* g, unsigned tag, unsigned v) {
-  __hip_atomic_store(g, ((unsigned long long)tag << 32) | v, RLX_AGENT);
-}
-
-// One wave reads NPL granules per lane (indices first + j*64 + lane) until every tag
-// matches; a pass re-reads only the granules that were not ready yet.
-template <int NPL>
-__device__ __forceinline__ void sweep(const gu64* g, int first, unsigned tag, unsigned (&v)[NPL], bool& dead,
-                                      gu32* err, unsigned code, int lane) {
-  static_assert(NPL <= 32, "ready mask is 32 bits");
-  constexpr unsigned all = NPL == 32 ? 0xffffffffu : ((1u << NPL) - 1);
-  unsigned ready = 0;
-  unsigned long long x[NPL];
-  for (unsigned spins = 0;;) {
-    // issue every outstanding load first (one round trip per pass), then check them
-#pragma unroll
-    for (int j = 0; j < NPL; ++j)
-      if (!((ready >> j) & 1)) x[j] = __hip_atomic_load(g + first + j * 64 + lane, RLX_AGENT);
-#pragma unroll
-    for (int j = 0; j < NPL; ++j)
-      if (!((ready >> j) & 1) && (unsigned)(x[j] >> 32) == tag) {
-        v[j] = (unsigned)x[j];
-        ready |= 1u << j;
-      }
-    if (__all(ready == all) || dead) return;
-    if (++spins > kSpinLimit / 4) {  // the longer sleep below: about the same wall-time bound
-      if (lane == 0) __hip_atomic_store(err, code, RLX_AGENT);
-      dead = true;
-      return;
-    }
-    // s_sleep(24) (~1500 clocks) between passes: the polls of 32 teams are a large share of
-    // the L2 traffic, and fewer of them lower every team's hand-off latency (tools/lstm_micro.py,
-    // per step: H = 512, B = 256: 6.82 us with s_sleep(1), 6.65 with 8, 6.28 with 24, 6.27 with
-    // 48; H = 256, B = 256: 3.01 / 2.97 / 2.97 / 3.46).  Spinning on one granule per lane first
-    // and sweeping once it is ready costs one more L2 round trip: 6.8 -> 8.3 us.
-    __builtin_amdgcn_s_sleep(24);
-  }
-}
 
 // Streaming activation traffic (gx / dout / acts / cs reads, acts / out / cs / hs / dz writes:
 // ~10 MB per step at H = 512, B = 256, each byte touched once per launch).  nt = 1 issues it
@@ -124,14 +76,6 @@ __device__ __forceinline__ float ld_dout(const float* dout, size_t idx, bool nt)
 template <int RS>
 __device__ __forceinline__ int swz(int row, int col) {
   return row * RS + ((((col >> 3) ^ (row & 7))) << 3) + (col & 7);
-}
-
-// block -> (team, slice): team members share blockIdx % 8 (same XCD under round-robin dealing)
-__device__ __forceinline__ bool team_of(int NC, int nteams, int& team, int& c) {
-  const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-  team = (q / NC) * 8 + xcd;
-  c = q % NC;
-  return team < nteams;
 }
 
 }  // namespace

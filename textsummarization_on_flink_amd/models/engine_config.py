@@ -8,8 +8,9 @@ engine is built); code can also pass a config explicitly.
 | Variable                  | Field              | Default / meaning |
 |---------------------------|--------------------|-------------------|
 | TSAMD_LSTM_PERSISTENT     | persistent_lstm    | 1: one persistent weight-resident launch per bi-LSTM pass; 0: per-step kernels |
+| TSAMD_DEC_PERSISTENT      | dec_persistent     | 1: the decoder forward loop as one persistent launch with per-tile hand-offs when ``dec_persistent_eligible`` (hidden 256, emb 128, projected row attention, B % 16 == 0, the whole grid co-resident); 0 or not eligible: three launches per step and row group |
 | TSAMD_ROW_ATTN            | row_attn           | auto (B >= 64): one workgroup per row; 0 / 1 force |
-| TSAMD_SPLIT               | split              | auto (2 groups from B = 256, 4 from B = 1024): decoder row groups on parallel streams |
+| TSAMD_SPLIT               | split              | auto (2 groups from B = 256, 4 from B = 1024): decoder row groups on parallel streams (forward loop: only when the persistent decoder launch is off or not eligible) |
 | TSAMD_SPLIT_BWD           | split_bwd          | auto (= split): row groups of the decoder backward loop |
 | TSAMD_FUSED_VOCAB_TRAIN   | fused_vocab_train  | 1: training vocab head with the logits only in MFMA accumulators; 0: library GEMM + ptr_loss |
 | TSAMD_FUSED_VOCAB         | fused_vocab_decode | 1: decode vocab head + top-k fused; 0: GEMM + final_topk |
@@ -41,6 +42,7 @@ def _tri(env: Mapping[str, str], name: str) -> Optional[bool]:
 @dataclass(frozen=True)
 class EngineConfig:
     persistent_lstm: bool = True
+    dec_persistent: bool = True
     row_attn: Optional[bool] = None
     split: int = 0
     split_bwd: int = 0
@@ -58,6 +60,7 @@ class EngineConfig:
         env = os.environ if env is None else env
         cfg = cls(
             persistent_lstm=_flag(env, "TSAMD_LSTM_PERSISTENT", True),
+            dec_persistent=_flag(env, "TSAMD_DEC_PERSISTENT", True),
             row_attn=_tri(env, "TSAMD_ROW_ATTN"),
             split=int(env.get("TSAMD_SPLIT", "0") or 0),
             split_bwd=int(env.get("TSAMD_SPLIT_BWD", "0") or 0),
@@ -74,3 +77,40 @@ class EngineConfig:
 
     def as_dict(self):
         return {f.name: getattr(self, f.name) for f in fields(self)}
+
+
+DEC_PERSISTENT_TEAM = 16  # workgroups per 16-row tile (csrc/kernels/decoder_persistent.hip)
+
+
+def dec_persistent_grid(B: int) -> int:
+    """Workgroups of the persistent decoder launch: teams of 16 dealt 8 at a time (one per XCD)."""
+    if B < 16 or B % 16:
+        return 0
+    return 8 * DEC_PERSISTENT_TEAM * (-(-(B // 16) // 8))
+
+
+def dec_persistent_eligible(H: int, E: int, A: int, B: int, T: int, proj_attn: bool, row_attn: bool,
+                            world: int = 1, capacity: int = 0, reserve_cus: int = 0) -> bool:
+    """Whether the decoder forward loop may run as ONE persistent launch (pure function of the
+    shape, the attention path, the world size and the device's resident capacity).
+
+    The kernel covers the headline family only (hidden 256, emb 128, A = 512, projected row
+    attention, whole 16-row tiles) and its workgroups wait for each other, so the whole grid must
+    be co-resident: ``capacity`` is the occupancy query's resident workgroup count, and with more
+    than one rank ``reserve_cus`` (the CUs an in-flight RCCL collective may hold) comes off it.
+    Not eligible means the three-kernel chains, never an error.
+
+    Invariant behind ``capacity``: it is one workgroup per CU of the whole device, and at the
+    headline batch of 256 the grid equals it with no margin.  That holds only while the launch has
+    the device to itself: the decoder forward runs on the step's single stream with nothing beside
+    it (the side streams of the step -- deferred weight gradients, the vocab dW -- all live in the
+    backward; the input copy stream carries DMA copies only), and no CU mask is in force.  Anything that may hold CUs during the forward (a new
+    side stream beside it, a CU mask, another process's kernels) must come off ``capacity`` here, as
+    RCCL's CUs do, or workgroups wait for unscheduled peers until the hand-off timeout."""
+    if not (proj_attn and row_attn):
+        return False
+    if (H, E, A) != (256, 128, 512) or B < 16 or B % 16 or not 1 <= T <= 2048:
+        return False
+    grid = dec_persistent_grid(B)
+    cap = capacity - (reserve_cus if world > 1 else 0)
+    return 0 < grid <= cap

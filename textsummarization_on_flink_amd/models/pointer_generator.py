@@ -29,7 +29,8 @@ import numpy as np
 import torch
 
 from ..ops import ops as _ops
-from .engine_config import EngineConfig
+from ..parallel.rccl_env import rccl_cu_reserve
+from .engine_config import EngineConfig, dec_persistent_eligible
 from .params import DEC, P, FlatParams, enc_prefix
 
 BF = torch.bfloat16
@@ -602,6 +603,10 @@ class HipPointerGenerator:
         # (row, step) pairs past the row's last loss-weighted step are skipped by the projected
         # kernels (their outputs are written as zeros; loss and gradients are unchanged)
         self.skip_pad = self.proj_attn and cfg.skip_pad_steps
+        # the forward loop as one persistent launch (decoder_persistent.hip) when the whole grid is
+        # co-resident; else the per-step chains of _decoder_forward_proj (set_world re-evaluates)
+        self.world = 1
+        self._dec_persistent_select()
         self.compact_vocab = self.skip_pad and cfg.fused_vocab_train and cfg.compact_vocab_grad and not cfg.deterministic \
             and H in (128, 256, 512) and (D * B) % 32 == 0
         w["F"] = z(B, T, A, dt=BF)
@@ -698,14 +703,35 @@ class HipPointerGenerator:
         w["nan_flag"] = z(1, dt=torch.int32)
         self.w = w
 
+    def _dec_persistent_select(self) -> None:
+        k = self.k
+        cap = int(k.dec_persistent_capacity()) if (self.cfg.dec_persistent and self.proj_attn) else 0
+        self.dec_persistent = self.cfg.dec_persistent and dec_persistent_eligible(
+            self.H, self.E, self.A, self.B, self.T, self.proj_attn, self.row_attn, self.world, cap,
+            rccl_cu_reserve())
+        if self.dec_persistent and getattr(self, "_dec_xbuf", None) is None:
+            self._dec_xbuf = torch.zeros(int(k.dec_persistent_xbuf(self.B)), dtype=torch.long, device=self.dev)
+
+    def set_world(self, world: int) -> None:
+        """Data-parallel trainers: RCCL collectives of ``world`` > 1 ranks may hold CUs, which come
+        off the capacity the persistent decoder launch needs (call before capturing graphs)."""
+        self.world = int(world)
+        self._dec_persistent_select()
+
     def check_lstm_err(self) -> None:
-        """Host sync: raise if a persistent-LSTM hand-off timed out in any launch since the
-        engine was built.  The word is sticky: those results were garbage, the optimizer
-        kernel skipped the update, and eval / decode must not report them."""
-        if int(self.w["lstm_err"].item()):
-            raise LstmHandoffError("persistent LSTM hand-off timed out (a workgroup was not co-resident); "
-                                   "results of that launch were discarded -- set TSAMD_LSTM_PERSISTENT=0 "
-                                   "(EngineConfig.persistent_lstm)")
+        """Host sync: raise if a hand-off of a persistent kernel timed out in any launch since the
+        engine was built: the persistent LSTM (codes 1 forward, 2 BPTT) or the persistent decoder
+        forward loop (code 3), which share the word.  It is sticky: those results were garbage, the
+        optimizer kernel skipped the update, and eval / decode must not report them."""
+        code = int(self.w["lstm_err"].item())
+        if code == 3:
+            raise LstmHandoffError("persistent decoder forward hand-off timed out (code 3: a workgroup was not "
+                                   "co-resident); results of that launch were discarded -- set "
+                                   "TSAMD_DEC_PERSISTENT=0 (EngineConfig.dec_persistent)")
+        if code:
+            raise LstmHandoffError(f"persistent LSTM hand-off timed out (code {code}: a workgroup was not "
+                                   "co-resident); results of that launch were discarded -- set "
+                                   "TSAMD_LSTM_PERSISTENT=0 (EngineConfig.persistent_lstm)")
 
     # ------------------------------------------------------------------ weights
     def pack(self):
@@ -1025,6 +1051,14 @@ class HipPointerGenerator:
         v, wc = self.f32["v"], self.f32["wc"]
         dlen = w["dlen"] if self.skip_pad else None
 
+        if self.dec_persistent:
+            self._dec_xbuf.zero_()  # hand-off tags must start at 0 every launch
+            k.dec_fwd_persistent(w["XG"], self.pk["KcT"], self.pk["WsT"], self.p[ATT_B], w["Cst"], w["Cb"], w["Hb"],
+                                 w["ACT"], w["S"], F, G, v, wc, w["COV"] if cov else None, lens, w["ATT"], w["ATTb"],
+                                 w["covloss"] if cov else None, w["GV"], w["GVb"], dlen, self._dec_xbuf,
+                                 w["lstm_err"], B, T, D, H, E, A)
+            return self._decoder_forward_proj_tail()
+
         def chain(r0, r1):
             Bg, rs = r1 - r0, slice(r0, r1)
             dl = dlen[rs] if dlen is not None else None
@@ -1040,6 +1074,11 @@ class HipPointerGenerator:
                                 dl, t, w["ATTb"][t][rs])
 
         self._row_groups(chain)
+        self._decoder_forward_proj_tail()
+
+    def _decoder_forward_proj_tail(self):
+        w, B, T, D, A = self.w, self.B, self.T, self.D, self.A
+        enc_out = self.enc[-1]["out"]
         w["X"][0].copy_(w["xe"][0])
         if D > 1:
             torch.add(w["xe"][1:], w["GV"][:D - 1], out=w["X"][1:])

@@ -107,6 +107,7 @@ class GraphTrainer:
                                       bounds=self.engine.phase_bounds(), average=False,
                                       compress=getattr(hps, "grad_compress", "none"))
         self.engine.grad_scale = 1.0 / self.info.world
+        self.engine.set_world(self.info.world)  # RCCL's CUs come off the persistent decoder's capacity
         self.engine.poison_on_lstm_err = self.info.enabled  # a hand-off timeout skips the step on every rank
         eng = self.engine
         self.lstm_exclusive = False

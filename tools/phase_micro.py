@@ -4,7 +4,14 @@ Builds the bench-shaped engine (defaults: pointer-gen + coverage, H=256, E=128, 
 V=50k, B=256), runs two eager steps so every buffer holds realistic values, then captures each
 phase of the step as its own hipGraph and times its replays with HIP events:
 encoder forward | decoder forward loop | head forward (+vocab loss) | backward_head |
-backward_mid | backward_tail | optimizer.  Prints one JSON line (ms per phase).
+backward_mid | backward_tail | optimizer.  Prints one JSON line (ms per phase).  When the
+persistent decoder launch is in use (``dec_persistent``: TSAMD_DEC_PERSISTENT, eligible shape),
+``decoder_fwd_chains`` is the same decoder forward with the switch off (the per-step chains); it
+is timed after the step's phases, behind a second encoder forward so both decoder phases start
+from the same cache state, and is not part of ``total``.  ``decoder_fwd_queued`` is the persistent
+decoder phase timed the same way right after it: both are enqueued while the GPU still works on the
+step, so neither contains the host's graph-launch time, which ``decoder_fwd`` (second phase after
+an idle GPU) can.
 
   python tools/phase_micro.py [--batch B] [--hidden H] [--enc T] [--layers L]
 """
@@ -47,6 +54,17 @@ def main():
               ("head_fwd", lambda: eng._head_forward(True)), ("backward_head", eng.backward_head),
               ("backward_mid", eng.backward_mid), ("backward_tail", eng.backward_tail),
               ("optimizer", eng.optimizer_step)]
+    nstep = len(phases)
+
+    def decoder_fwd_chains():
+        eng.dec_persistent = False
+        try:
+            eng._decoder_forward()
+        finally:
+            eng.dec_persistent = True
+
+    if eng.dec_persistent:
+        phases.append(("decoder_fwd_chains", decoder_fwd_chains))
     graphs = []
     pool = torch.cuda.graph_pool_handle()
     s = torch.cuda.Stream()
@@ -64,20 +82,37 @@ def main():
                 fn()
             graphs.append(g)
     torch.cuda.synchronize()
-    res = {"batch": a.batch, "hidden": a.hidden, "enc": a.enc, "layers": a.layers}
+    res = {"batch": a.batch, "hidden": a.hidden, "enc": a.enc, "layers": a.layers,
+           "dec_persistent": bool(eng.dec_persistent)}
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(phases) + 1)]
+    ev_x = torch.cuda.Event(enable_timing=True)
+    ev_y, tot_y = [torch.cuda.Event(enable_timing=True) for _ in range(2)], 0.0
     tot = [0.0] * len(phases)
     for _ in range(a.iters):
         ev[0].record()
-        for i, g in enumerate(graphs):
+        for i, g in enumerate(graphs[:nstep]):
             g.replay()
             ev[i + 1].record()
+        if len(phases) > nstep:  # the chains right after an encoder forward, as the persistent launch above
+            graphs[0].replay()
+            ev_x.record()
+            graphs[nstep].replay()
+            ev[nstep + 1].record()
+            graphs[0].replay()
+            ev_y[0].record()
+            graphs[1].replay()
+            ev_y[1].record()
         torch.cuda.synchronize()
-        for i in range(len(phases)):
+        for i in range(nstep):
             tot[i] += ev[i].elapsed_time(ev[i + 1])
+        if len(phases) > nstep:
+            tot[nstep] += ev_x.elapsed_time(ev[nstep + 1])
+            tot_y += ev_y[0].elapsed_time(ev_y[1])
     for (n, _), t in zip(phases, tot):
         res[n] = round(t / a.iters, 3)
-    res["total"] = round(sum(tot) / a.iters, 3)
+    if len(phases) > nstep:
+        res["decoder_fwd_queued"] = round(tot_y / a.iters, 3)
+    res["total"] = round(sum(tot[:nstep]) / a.iters, 3)
     print(json.dumps(res), flush=True)
 
 
