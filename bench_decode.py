@@ -32,6 +32,8 @@ def main():
     ap.add_argument("--enc", type=int, default=400, help="max encoder steps (config #5: 800)")
     ap.add_argument("--unfused-step", action="store_true",
                     help="A/B: the 8-launch decode step (separate beam_step) instead of the fused beam tail")
+    ap.add_argument("--block_ngram_repeat", type=int, default=0,
+                    help="n-gram blocking in the beam bookkeeping (3 = trigram blocking; 0 = off)")
     args = ap.parse_args()
     import torch
     from textsummarization_on_flink_amd.config import HParams
@@ -40,7 +42,8 @@ def main():
     from textsummarization_on_flink_amd.models.params import build_params
 
     hps = HParams(mode="decode", batch_size=args.articles, beam_size=args.beam, coverage=True, vocab_size=args.vocab,
-                  hidden_dim=args.hidden, enc_layers=args.layers, max_enc_steps=args.enc)
+                  hidden_dim=args.hidden, enc_layers=args.layers, max_enc_steps=args.enc,
+                  block_ngram_repeat=args.block_ngram_repeat)
     corpus = SyntheticCorpus(vocab_size=args.vocab, seed=7)
     vocab = corpus.vocab(args.vocab)
     batches = make_batches(hps, vocab, corpus, args.batches + args.warmup, pad_enc_to=hps.max_enc_steps)
@@ -83,7 +86,8 @@ def main():
                                           f"dec<=100 vocab={args.vocab} enc_layers={args.layers}",
                                  "beam": args.beam, "articles_per_batch": args.articles,
                                  "rows": args.articles * args.beam, "graph": not args.no_graph,
-                                 "pipelined": args.pipelined, "fused_step": bool(dec.fused_step)}}))
+                                 "pipelined": args.pipelined, "fused_step": bool(dec.fused_step),
+                                 "block_ngram_repeat": args.block_ngram_repeat}}))
 
 
 if __name__ == "__main__":

@@ -959,10 +959,27 @@ void vocab_span_probe(const Tensor& X, const Tensor& WT, const Tensor& bias, con
                           (int)probe, stream());
 }
 
+// n-gram blocking (block_ngram_repeat = ngram > 1) of the beam bookkeeping: the hypotheses' token
+// sequences, two ping-pong int32 [R][P] buffers, P >= max_dec + 1 and a multiple of 4 (the
+// article's ban table, beam * P ints, lives in LDS).  ngram <= 1: off, the buffers may be absent.
+NgSeq ng_seq(const OT& seq0, const OT& seq1, int64_t ngram, int64_t R, int64_t beam, int64_t max_dec) {
+  if (ngram <= 1) return NgSeq{{nullptr, nullptr}, 0, 0};
+  TORCH_CHECK(seq0.has_value() && seq0->defined() && seq1.has_value() && seq1->defined(),
+              "n-gram blocking needs the seq0 / seq1 token-sequence buffers");
+  chk(*seq0, I32, "seq0"); chk(*seq1, I32, "seq1");
+  const int64_t pitch = R > 0 ? seq0->numel() / R : 0;
+  TORCH_CHECK(pitch >= max_dec + 1 && pitch % 4 == 0 && beam * pitch <= NG_BAN_MAX && ngram <= (1 << 20),
+              "n-gram blocking: seq is [R][P] with P >= max_dec + 1, P % 4 == 0 and beam * P <= ", NG_BAN_MAX);
+  numel_eq(*seq0, R * pitch, "seq0"); numel_eq(*seq1, R * pitch, "seq1");
+  TORCH_CHECK(seq0->data_ptr() != seq1->data_ptr(), "seq0 and seq1 must be two buffers");
+  return NgSeq{{P<int>(*seq0), P<int>(*seq1)}, (int)pitch, (int)ngram};
+}
+
 // One beam-decode step's head: vocab_topk (p_gen inside when the pointer inputs are given) with
 // the beam bookkeeping fused into the select kernel's per-article tail (replaces vocab_topk_pg +
 // beam_step).  The step counter was advanced at the start of the step (dec_cell_fwd_beam).
-void vocab_topk_beam(const Tensor& X, const Tensor& WT, const Tensor& bias, const OT& ctx, const OT& c, const OT& h,
+// seq0 / seq1 / ngram: n-gram blocking (see ng_seq), off for ngram <= 1.
+void vocab_topk_beam_ng(const Tensor& X, const Tensor& WT, const Tensor& bias, const OT& ctx, const OT& c, const OT& h,
                      const OT& x, const OT& pg_w, const OT& pg_b, const OT& pg_out, const OT& attn, const Tensor& ext,
                      const Tensor& lens, const Tensor& out_ids, const Tensor& out_lp, const Tensor& logits,
                      const Tensor& part_ms, const Tensor& lp_sum, const Tensor& latest, const Tensor& gidx,
@@ -971,7 +988,7 @@ void vocab_topk_beam(const Tensor& X, const Tensor& WT, const Tensor& bias, cons
                      const Tensor& step, const Tensor& art_ctr, const Tensor& gran, const Tensor& err,
                      const OT& att_hist, const OT& pg_hist, int64_t R,
                      int64_t V, int64_t H, int64_t T, int64_t K, int64_t beam, int64_t A, int64_t E, int64_t stop_id,
-                     int64_t min_dec, int64_t max_dec) {
+                     int64_t min_dec, int64_t max_dec, const OT& seq0, const OT& seq1, int64_t ngram) {
   chk(X, BF, "X"); chk(WT, BF, "WT"); chk(bias, F32, "bias"); chk(ext, I32, "ext"); chk(lens, I32, "lens");
   chk(out_ids, I32, "out_ids"); chk(out_lp, F32, "out_lp"); chk(logits, F32, "logits"); chk(part_ms, F32, "part_ms");
   const int64_t nt = vocab_topk_tiles((int)V, (int)H), Na = R / beam;
@@ -1010,9 +1027,26 @@ void vocab_topk_beam(const Tensor& X, const Tensor& WT, const Tensor& bias, cons
                     P<int>(step), (unsigned*)P<int>(art_ctr), (unsigned long long*)gran.data_ptr(), P<int>(err),
                     PO<float>(attn), PO<float>(att_hist), PO<float>(pg_out),
                     PO<float>(pg_hist), (int)T, (int)Na, (int)beam, (int)K, (int)stop_id, (int)min_dec, (int)max_dec};
+  const NgSeq ng = ng_seq(seq0, seq1, ngram, R, beam, max_dec);
   launch_vocab_topk(P<bf16>(X), P<bf16>(WT), P<float>(bias), nullptr, ptr ? PO<float>(attn) : nullptr, P<int>(ext),
                     P<int>(lens), P<int>(out_ids), P<float>(out_lp), P<float>(logits), P<float>(part_ms), R, V, H, T, K,
-                    beam, pgi, stream(), &bt);
+                    beam, pgi, stream(), &bt, &ng);
+}
+
+void vocab_topk_beam(const Tensor& X, const Tensor& WT, const Tensor& bias, const OT& ctx, const OT& c, const OT& h,
+                     const OT& x, const OT& pg_w, const OT& pg_b, const OT& pg_out, const OT& attn, const Tensor& ext,
+                     const Tensor& lens, const Tensor& out_ids, const Tensor& out_lp, const Tensor& logits,
+                     const Tensor& part_ms, const Tensor& lp_sum, const Tensor& latest, const Tensor& gidx,
+                     const Tensor& tok_hist, const Tensor& par_hist, const Tensor& done, const Tensor& res_count,
+                     const Tensor& res_score, const Tensor& res_len, const Tensor& res_step, const Tensor& res_par,
+                     const Tensor& step, const Tensor& art_ctr, const Tensor& gran, const Tensor& err,
+                     const OT& att_hist, const OT& pg_hist, int64_t R,
+                     int64_t V, int64_t H, int64_t T, int64_t K, int64_t beam, int64_t A, int64_t E, int64_t stop_id,
+                     int64_t min_dec, int64_t max_dec) {
+  vocab_topk_beam_ng(X, WT, bias, ctx, c, h, x, pg_w, pg_b, pg_out, attn, ext, lens, out_ids, out_lp, logits, part_ms,
+                     lp_sum, latest, gidx, tok_hist, par_hist, done, res_count, res_score, res_len, res_step, res_par,
+                     step, art_ctr, gran, err, att_hist, pg_hist, R, V, H, T, K, beam, A, E, stop_id, min_dec, max_dec,
+                     c10::nullopt, c10::nullopt, 0);
 }
 
 // decoder cell of a beam-decode step with the parent / token gathers inside (dec_cell_fwd +
@@ -1078,13 +1112,13 @@ void attn_fwd_row_beam(const Tensor& F, const Tensor& E, const Tensor& s, const 
 // Advances step[0] by one (the last block to finish) when ctr (one zeroed uint32 scratch word)
 // is given; without ctr, beam_gather advanced it at the start of the decode step (t = step - 1).
 // att/att_hist/pg/pg_hist (optional): this step's attention rows and p_gen copied into row
-// min(step, max_dec - 1) of the histories.
-void beam_step(const Tensor& top_ids, const Tensor& top_lp, const Tensor& lp_sum, const Tensor& latest,
+// min(step, max_dec - 1) of the histories.  seq0 / seq1 / ngram: n-gram blocking (see ng_seq).
+void beam_step_ng(const Tensor& top_ids, const Tensor& top_lp, const Tensor& lp_sum, const Tensor& latest,
                const Tensor& gidx, const Tensor& tok_hist, const Tensor& par_hist, const Tensor& done,
                const Tensor& res_count, const Tensor& res_score, const Tensor& res_len, const Tensor& res_step,
                const Tensor& res_par, const Tensor& step, const OT& ctr, const OT& att, const OT& att_hist,
                const OT& pg, const OT& pg_hist, int64_t T, int64_t Na, int64_t beam, int64_t K, int64_t stop_id,
-               int64_t min_dec, int64_t max_dec) {
+               int64_t min_dec, int64_t max_dec, const OT& seq0, const OT& seq1, int64_t ngram) {
   chk(top_ids, I32, "top_ids"); chk(top_lp, F32, "top_lp"); chk(lp_sum, F32, "lp_sum"); chk(latest, I32, "latest");
   chk(gidx, I32, "gidx"); chk(tok_hist, I32, "tok_hist"); chk(par_hist, I32, "par_hist"); chk(done, I32, "done");
   chk(res_count, I32, "res_count"); chk(res_score, F32, "res_score"); chk(res_len, I32, "res_len");
@@ -1100,11 +1134,23 @@ void beam_step(const Tensor& top_ids, const Tensor& top_lp, const Tensor& lp_sum
               (!pg.has_value() || att.has_value()), "att/att_hist and pg/pg_hist come in pairs (pg needs att)");
   chko(att, F32, R * T, "att"); chko(att_hist, F32, max_dec * R * T, "att_hist");
   chko(pg, F32, R, "pg"); chko(pg_hist, F32, max_dec * R, "pg_hist");
+  const NgSeq ng = ng_seq(seq0, seq1, ngram, R, beam, max_dec);
   launch_beam_step(P<int>(top_ids), P<float>(top_lp), P<float>(lp_sum), P<int>(latest), P<int>(gidx), P<int>(tok_hist),
                    P<int>(par_hist), P<int>(done), P<int>(res_count), P<float>(res_score), P<int>(res_len),
                    P<int>(res_step), P<int>(res_par), P<int>(step), (unsigned*)PO<int>(ctr), PO<float>(att),
                    PO<float>(att_hist), PO<float>(pg), PO<float>(pg_hist), (int)T, Na, beam, K, stop_id, min_dec,
-                   max_dec, stream());
+                   max_dec, stream(), &ng);
+}
+
+void beam_step(const Tensor& top_ids, const Tensor& top_lp, const Tensor& lp_sum, const Tensor& latest,
+               const Tensor& gidx, const Tensor& tok_hist, const Tensor& par_hist, const Tensor& done,
+               const Tensor& res_count, const Tensor& res_score, const Tensor& res_len, const Tensor& res_step,
+               const Tensor& res_par, const Tensor& step, const OT& ctr, const OT& att, const OT& att_hist,
+               const OT& pg, const OT& pg_hist, int64_t T, int64_t Na, int64_t beam, int64_t K, int64_t stop_id,
+               int64_t min_dec, int64_t max_dec) {
+  beam_step_ng(top_ids, top_lp, lp_sum, latest, gidx, tok_hist, par_hist, done, res_count, res_score, res_len, res_step,
+               res_par, step, ctr, att, att_hist, pg, pg_hist, T, Na, beam, K, stop_id, min_dec, max_dec, c10::nullopt,
+               c10::nullopt, 0);
 }
 
 void beam_gather(const Tensor& gidx, const Tensor& latest, const Tensor& c_src, const Tensor& h_src,
@@ -1280,6 +1326,7 @@ TORCH_LIBRARY(tsamd, m) {
   m.def("final_topk", &final_topk);
   m.def("topk_parts", &topk_parts);
   m.def("beam_step", &beam_step);
+  m.def("beam_step_ng", &beam_step_ng);
   m.def("beam_gather", &beam_gather);
   m.def("linear2", &linear2);
   m.def("pgen", &pgen);
@@ -1290,6 +1337,7 @@ TORCH_LIBRARY(tsamd, m) {
   m.def("vocab_select_stamps", &vocab_select_stamps);
   m.def("lstm_bwd_stamps", &lstm_bwd_stamps);
   m.def("vocab_topk_beam", &vocab_topk_beam);
+  m.def("vocab_topk_beam_ng", &vocab_topk_beam_ng);
   m.def("dec_cell_fwd_beam", &dec_cell_fwd_beam);
   m.def("beam_sproj_xmerge", &beam_sproj_xmerge);
   m.def("attn_fwd_row_beam", &attn_fwd_row_beam);

@@ -264,6 +264,10 @@ __global__ __launch_bounds__(TOPK_THREADS) void final_topk_merge_kernel(
   }
 }
 
+// n-gram blocking (beam_common.h): instantiated with one trailing NgSeq argument -- the
+// hypotheses' token sequences, parity from t; without it the kernel and its arguments are
+// exactly the plain bookkeeping
+template <typename... NGA>
 __global__ __launch_bounds__(64) void beam_step_kernel(
     const int* __restrict__ top_ids, const float* __restrict__ top_lp,  // [R][K]
     float* __restrict__ lp_sum,        // [R] in: per live hyp; out: per new hyp
@@ -276,10 +280,14 @@ __global__ __launch_bounds__(64) void beam_step_kernel(
     int* __restrict__ step, unsigned* __restrict__ ctr,  // step advanced by the last block to finish
     const float* __restrict__ att, float* __restrict__ att_hist,  // optional: [R][T] -> [maxD][R][T]
     const float* __restrict__ pg, float* __restrict__ pg_hist,    // optional: [R] -> [maxD][R]
-    int T, int beam, int K, int stop_id, int min_dec, int max_dec) {
+    int T, int beam, int K, int stop_id, int min_dec, int max_dec, NGA... nga) {
+  constexpr bool NG = sizeof...(NGA) == 1;
+  const NgSeq ng = ng_of(nga...);
   __shared__ float cval[64];
   __shared__ int cid[64];
   __shared__ int srt[64];
+  __shared__ __attribute__((aligned(16))) int ban[NG ? NG_BAN_MAX : 4];
+  __shared__ int adv_par[NG ? BEAM_CAND_MAX : 1], adv_tok[NG ? BEAM_CAND_MAX : 1];
   const int a = blockIdx.x, lane = threadIdx.x;
   const int base = a * beam;
   const size_t R = (size_t)gridDim.x * beam;
@@ -289,11 +297,12 @@ __global__ __launch_bounds__(64) void beam_step_kernel(
   // ctr == nullptr: beam_gather advanced the counter at the start of this decode step
   const int t = ctr ? *step : *step - 1;
   const int is_done = done[a], nres0 = res_count[a];
-  float tot = -INFINITY;
+  float tot = -INFINITY, lps = 0.f;
   int tid_cand = 0;
   if (lane < beam * K) {
     const int i = lane / K, j = lane % K;
-    tot = lp_sum[base + i] + top_lp[(size_t)(base + i) * K + j];
+    lps = lp_sum[base + i];
+    tot = lps + top_lp[(size_t)(base + i) * K + j];
     tid_cand = top_ids[(size_t)(base + i) * K + j];
   }
   if (att_hist) {  // attention / p_gen history for the visualiser, row t (clamped)
@@ -304,9 +313,18 @@ __global__ __launch_bounds__(64) void beam_step_kernel(
   if (is_done || t >= max_dec) {
     if (lane < beam) gidx[base + lane] = base + lane;
   } else {
-    beam_step_body(top_ids, top_lp, lp_sum, latest, gidx, tok_hist, par_hist, done, res_count, res_score, res_len,
-                   res_step, res_par, cval, cid, srt, a, lane, t, base, beam, K, stop_id, min_dec, tot, tid_cand,
-                   nres0, (int)gridDim.x);
+    if constexpr (NG) {
+      ngram_ban_build(ng.seq[t & 1], ban, base, beam, ng.P, ng.n, t, (int)R);
+      __syncthreads();
+      if (lane < beam * K && ngram_banned(ban, lane / K, ng.P, t, tid_cand)) tot = lps + BLOCKED_LP;
+    }
+    beam_step_body<NG>(top_ids, top_lp, lp_sum, latest, gidx, tok_hist, par_hist, done, res_count, res_score, res_len,
+                       res_step, res_par, cval, cid, srt, a, lane, t, base, beam, K, stop_id, min_dec, tot, tid_cand,
+                       nres0, (int)gridDim.x, adv_par, adv_tok);
+    if constexpr (NG) {
+      __syncthreads();  // adv_par / adv_tok written by lanes < beam
+      ngram_seq_advance(ng.seq[t & 1], ng.seq[(t + 1) & 1], adv_par, adv_tok, base, beam, ng.P, t, (int)R);
+    }
   }
   // grid-wide step advance (standalone use): every block read *step above; the last one to
   // arrive bumps it -- a fence plus one same-address atomic per article (64 serialised L2
@@ -384,8 +402,13 @@ void launch_beam_step(const int* top_ids, const float* top_lp, float* lp_sum, in
                       int* par_hist, int* done, int* res_count, float* res_score, int* res_len, int* res_step,
                       int* res_par, int* step, unsigned* ctr, const float* att, float* att_hist, const float* pg,
                       float* pg_hist, int T, int Na, int beam, int K, int stop_id, int min_dec, int max_dec,
-                      hipStream_t st) {
-  hipLaunchKernelGGL(beam_step_kernel, dim3(Na), dim3(64), 0, st, top_ids, top_lp, lp_sum, latest, gidx, tok_hist,
-                     par_hist, done, res_count, res_score, res_len, res_step, res_par, step, ctr, att, att_hist, pg,
-                     pg_hist, T, beam, K, stop_id, min_dec, max_dec);
+                      hipStream_t st, const NgSeq* ng) {
+  if (ng && ng->n > 1)
+    hipLaunchKernelGGL(beam_step_kernel<NgSeq>, dim3(Na), dim3(64), 0, st, top_ids, top_lp, lp_sum, latest, gidx,
+                       tok_hist, par_hist, done, res_count, res_score, res_len, res_step, res_par, step, ctr, att,
+                       att_hist, pg, pg_hist, T, beam, K, stop_id, min_dec, max_dec, *ng);
+  else
+    hipLaunchKernelGGL(beam_step_kernel<>, dim3(Na), dim3(64), 0, st, top_ids, top_lp, lp_sum, latest, gidx,
+                       tok_hist, par_hist, done, res_count, res_score, res_len, res_step, res_par, step, ctr, att,
+                       att_hist, pg, pg_hist, T, beam, K, stop_id, min_dec, max_dec);
 }

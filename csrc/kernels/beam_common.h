@@ -8,13 +8,74 @@
 
 #define BEAM_CAND_MAX 16  // max beam (new hypotheses kept per step)
 
+// ------------------------------------------------------------------ n-gram blocking
+// block_ngram_repeat = n (decode/beam_search.py ngram_blocked): candidate w of a hypothesis with
+// tokens s[0..t] is blocked iff some e in [n - 1, t] has s[e] == w and s[e-n+1 .. e-1] equal to
+// the hypothesis' last n - 1 tokens.  A blocked candidate's step log-prob becomes BLOCKED_LP: it
+// ranks behind every unblocked one and is taken only when nothing else is left.
+#define BLOCKED_LP (-1e20f)
+// the kernels' optional trailing NgSeq argument (a pack of zero or one)
+__device__ __forceinline__ NgSeq ng_of() { return NgSeq{}; }
+__device__ __forceinline__ NgSeq ng_of(const NgSeq& x) { return x; }
+
+// The candidate-independent half of the test, once per article by the whole workgroup:
+// ban[i * P + e] = s_i[e] where the n - 1 tokens before e match hypothesis i's suffix, else -1
+// (also for e in (t, next multiple of 4), so the candidates scan whole int4s).  The sequences
+// come from global memory (written by the previous step's launch; independent loads, L2).
+__device__ __forceinline__ void ngram_ban_build(const int* __restrict__ seq_in, int* ban, int base, int beam, int P,
+                                                int n, int t, int R) {
+  const int t4 = (t + 4) & ~3;  // t + 1 tokens rounded up: <= P
+  for (int idx = threadIdx.x; idx < beam * t4; idx += blockDim.x) {
+    const int i = idx / t4, e = idx - i * t4;
+    const int* s = seq_in + (size_t)DCHECK_IDX(base + i, 0, R, CHK_BEAM_SEQ) * P;
+    DCHECK_IN(e, 0, P, CHK_BEAM_SEQ);
+    int v = -1;
+    if (e >= n - 1 && e <= t) {
+      bool m = true;
+      for (int k = 1; k < n; ++k) m &= s[e - k] == s[t + 1 - k];
+      if (m) v = s[e];
+    }
+    ban[i * P + e] = v;
+  }
+}
+
+// candidate (hypothesis i, token w >= 0): is w in the hypothesis' ban list?
+__device__ __forceinline__ bool ngram_banned(const int* ban, int i, int P, int t, int w) {
+  const int4* b = reinterpret_cast<const int4*>(ban + i * P);  // ban 16-byte aligned, P % 4 == 0
+  bool hit = false;
+  for (int q = 0; q <= (t >> 2); ++q) {
+    const int4 v = b[q];
+    hit |= (v.x == w) | (v.y == w) | (v.z == w) | (v.w == w);
+  }
+  return hit;
+}
+
+// seq_out[base + k] = seq_in[base + parent of k][0..t] ++ [token of k] for the new hypotheses
+// (adv_par / adv_tok: LDS, written by beam_step_body), by the whole workgroup
+__device__ __forceinline__ void ngram_seq_advance(const int* __restrict__ seq_in, int* __restrict__ seq_out,
+                                                  const int* adv_par, const int* adv_tok, int base, int beam, int P,
+                                                  int t, int R) {
+  const int L1 = t + 2;  // <= max_dec + 1 <= P
+  for (int idx = threadIdx.x; idx < beam * L1; idx += blockDim.x) {
+    const int k = idx / L1, e = idx - k * L1;
+    const int par = (int)DCHECK_IDX(adv_par[k], 0, beam, CHK_BEAM_SEQ);
+    DCHECK_IN(e, 0, P, CHK_BEAM_SEQ);
+    DCHECK_IN(base + k, 0, R, CHK_BEAM_SEQ);
+    seq_out[(size_t)(base + k) * P + e] = e <= t ? seq_in[(size_t)(base + par) * P + e] : adv_tok[k];
+  }
+}
+
 // ------------------------------------------------------------------ beam bookkeeping
+// NG: also leaves each new hypothesis' parent slot and token in adv_par / adv_tok (LDS, [beam])
+// for ngram_seq_advance
+template <bool NG = false>
 __device__ __forceinline__ void beam_step_body(
     const int* __restrict__ top_ids, const float* __restrict__ top_lp, float* __restrict__ lp_sum,
     int* __restrict__ latest, int* __restrict__ gidx, int* __restrict__ tok_hist, int* __restrict__ par_hist,
     int* __restrict__ done, int* __restrict__ res_count, float* __restrict__ res_score, int* __restrict__ res_len,
     int* __restrict__ res_step, int* __restrict__ res_par, float* cval, int* cid, int* srt, int a, int lane, int t,
-    int base, int beam, int K, int stop_id, int min_dec, float tot, int tid_cand, int nres0, int Na) {
+    int base, int beam, int K, int stop_id, int min_dec, float tot, int tid_cand, int nres0, int Na,
+    int* adv_par = nullptr, int* adv_tok = nullptr) {
   // tot / tid_cand / nres0: this lane's candidate and the result count, loaded by the caller
   // in the same memory round trip as the step counter and the done flag
   const int norig = t == 0 ? 1 : beam;
@@ -83,6 +144,10 @@ __device__ __forceinline__ void beam_step_body(
     gidx[base + k] = base + par;
     tok_hist[(size_t)t * Na * beam + base + k] = nh > 0 ? ntok[kk] : stop_id;
     par_hist[(size_t)t * Na * beam + base + k] = par;
+    if constexpr (NG) {
+      adv_par[k] = par;
+      adv_tok[k] = nh > 0 ? ntok[kk] : stop_id;
+    }
   }
   (void)nres_s;
 }
@@ -96,12 +161,20 @@ __device__ __forceinline__ void beam_step_body(
 // XCDs): the tail polls them until every tag is this step's -- no device-scope fence (on this
 // GPU a release fence writes back the whole L2).  Every thread of the workgroup calls it (it
 // contains block barriers); lanes < 64 do the work.  err: set when a poll times out.
-__device__ __forceinline__ void beam_article_tail(const BeamTail& bt, int a, float* cval, int* cid, int* srt) {
+// NG (n-gram blocking): the whole workgroup builds the article's ban table (ban: >= beam * ng.P
+// ints of LDS, 16-byte aligned) before the poll and advances the sequences after the bookkeeping
+// (adv: 2 * BEAM_CAND_MAX ints of LDS).
+template <bool NG = false>
+__device__ __forceinline__ void beam_article_tail(const BeamTail& bt, int a, float* cval, int* cid, int* srt,
+                                                  const NgSeq& ng = NgSeq{}, int* ban = nullptr, int* adv = nullptr) {
   const int lane = threadIdx.x, beam = bt.beam, K = bt.K, base = a * beam;
   const size_t R = (size_t)bt.Na * beam;
   const int t = *bt.step - 1;
   const unsigned tag = (unsigned)(*bt.step) & 0x7fffu;
   const int is_done = bt.done[a], nres0 = bt.res_count[a];
+  if constexpr (NG) {
+    if (!(is_done || t >= bt.max_dec)) ngram_ban_build(ng.seq[t & 1], ban, base, beam, ng.P, ng.n, t, (int)R);
+  }
   float tot = -INFINITY;
   int tid_cand = 0;
   if (lane < beam * K) {
@@ -128,6 +201,15 @@ __device__ __forceinline__ void beam_article_tail(const BeamTail& bt, int a, flo
   }
   if (is_done || t >= bt.max_dec) {
     if (lane < beam) bt.gidx[base + lane] = base + lane;
+  } else if constexpr (NG) {
+    __syncthreads();  // the ban table is complete
+    if (lane < beam * K && ngram_banned(ban, lane / K, ng.P, t, tid_cand))
+      tot = bt.lp_sum[base + lane / K] + BLOCKED_LP;
+    beam_step_body<true>(nullptr, nullptr, bt.lp_sum, bt.latest, bt.gidx, bt.tok_hist, bt.par_hist, bt.done,
+                         bt.res_count, bt.res_score, bt.res_len, bt.res_step, bt.res_par, cval, cid, srt, a, lane, t,
+                         base, beam, K, bt.stop_id, bt.min_dec, tot, tid_cand, nres0, bt.Na, adv, adv + BEAM_CAND_MAX);
+    __syncthreads();  // the new hypotheses' parents / tokens written by lanes < beam
+    ngram_seq_advance(ng.seq[t & 1], ng.seq[(t + 1) & 1], adv, adv + BEAM_CAND_MAX, base, beam, ng.P, t, (int)R);
   } else {
     beam_step_body(nullptr, nullptr, bt.lp_sum, bt.latest, bt.gidx, bt.tok_hist, bt.par_hist, bt.done, bt.res_count,
                    bt.res_score, bt.res_len, bt.res_step, bt.res_par, cval, cid, srt, a, lane, t, base, beam, K,

@@ -15,6 +15,7 @@
 #define CHK_LOSS_LEN 5     // pointer loss / row finalise: encoder length in [0, T]
 #define CHK_BEAM_PARENT 6  // beam gather: parent row in [0, R)
 #define CHK_BEAM_TOKEN 7   // beam gather: latest token id >= 0
+#define CHK_BEAM_SEQ 8     // n-gram blocking: token-sequence row in [0, R), position in [0, P), parent in [0, beam)
 
 #ifdef TSAMD_DEBUG
 extern __device__ unsigned tsamd_dbg[4];

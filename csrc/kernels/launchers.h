@@ -91,12 +91,21 @@ int opt_nparts();
 void launch_final_topk(const float* logits, const float* bias, const float* pgen, const float* attn, const int* ext,
                        const int* lens, int* out_ids, float* out_lp, float* part_ms, float* part_v, int* part_i, int R,
                        int V, int T, int K, int beam, hipStream_t st);
+// n-gram blocking of the beam bookkeeping (beam_common.h): the hypotheses' token sequences,
+// ping-pong [R][P] each -- step t reads seq[t & 1] (tokens 0..t, [START] first) and writes
+// seq[(t + 1) & 1].  n <= 1 (or no NgSeq): off, the kernels without it run.
+#define NG_BAN_MAX 4096  // beam * P ints of LDS for the per-article ban table
+struct NgSeq {
+  int* seq[2];
+  int P;  // row pitch: >= max_dec + 1, a multiple of 4
+  int n;
+};
 int topk_split(int V);
 void launch_beam_step(const int* top_ids, const float* top_lp, float* lp_sum, int* latest, int* gidx, int* tok_hist,
                       int* par_hist, int* done, int* res_count, float* res_score, int* res_len, int* res_step,
                       int* res_par, int* step, unsigned* ctr, const float* att, float* att_hist, const float* pg,
                       float* pg_hist, int T, int Na, int beam, int K, int stop_id, int min_dec, int max_dec,
-                      hipStream_t st);
+                      hipStream_t st, const NgSeq* ng = nullptr);
 void launch_beam_gather(const int* gidx, const int* latest, const float* c_src, const bf16* h_src,
                         const float* ctx_src, const float* a_src, const float* cov_src, const float* XGtab,
                         const float* Xtab, float* c_out, bf16* h_out, float* ctx_out, bf16* ctxb_out, float* cov_out,
@@ -151,7 +160,7 @@ struct PgIn {
 void launch_vocab_topk(const bf16* X, const bf16* WT, const float* bias, const float* pgen, const float* attn,
                        const int* ext, const int* lens, int* out_ids, float* out_lp, float* logits, float* part_ms,
                        int R, int V, int H, int T, int K, int beam, PgIn pgi, hipStream_t st,
-                       const BeamTail* bt = nullptr);
+                       const BeamTail* bt = nullptr, const NgSeq* ng = nullptr);
 int vocab_train_tiles(int V, int H);
 void launch_vocab_train_fwd(const bf16* X, int ldx, const bf16* WT, const float* bias, const int* target, float* part,
                             float* zg, float* lse, float* pv, int N, int V, int H, const int* vblk, const int* vblk_n,

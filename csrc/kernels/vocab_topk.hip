@@ -565,12 +565,15 @@ __device__ unsigned long long* vs_stamps = nullptr;
       if (tid == 0) vs_stamps[(size_t)r * 16 + (k)] = __builtin_amdgcn_s_memtime();    \
     }                                                                                  \
   } while (0)
-template <bool STAMP = false>
+// n-gram blocking in the beam tail (beam_common.h): instantiated with one trailing NgSeq argument
+// (without it the kernel and its arguments are exactly the plain one); its ban table reuses ci
+template <bool STAMP = false, typename... NGA>
 __global__ __launch_bounds__(VS_THREADS) void vocab_select_kernel(
     const float* __restrict__ logits, const float* __restrict__ part_ms, const float* __restrict__ pgen,
     const float* __restrict__ attn, const int* __restrict__ ext, const int* __restrict__ lens,
     int* __restrict__ out_ids, float* __restrict__ out_lp, int V, int T, int K, int beam, int nt, int tcols, PgIn pgi,
-    BeamTail bt, int span) {  // span: partials of vocab_logits_span_kernel (nt = NW waves, [G][R][8], vp_lo columns)
+    BeamTail bt, int span, NGA... nga) {  // span: partials of vocab_logits_span_kernel (nt = NW waves, [G][R][8], vp_lo columns)
+  constexpr bool NG = sizeof...(NGA) == 1;
   __shared__ float bt_cval[64];
   __shared__ int bt_cid[64], bt_srt[64];
   __shared__ int bt_last;
@@ -813,7 +816,10 @@ __global__ __launch_bounds__(VS_THREADS) void vocab_select_kernel(
     __syncthreads();
     if (bt_last) {
       if (tid == 0) __hip_atomic_store(&bt.art_ctr[art], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      beam_article_tail(bt, art, bt_cval, bt_cid, bt_srt);
+      if constexpr (NG)  // (ci, cv: every read of them ended before the barriers above)
+        beam_article_tail<true>(bt, art, bt_cval, bt_cid, bt_srt, ng_of(nga...), ci, reinterpret_cast<int*>(cv));
+      else
+        beam_article_tail(bt, art, bt_cval, bt_cid, bt_srt);
     }
   }
   VS_ST(12);
@@ -855,9 +861,12 @@ int vocab_topk_tiles(int V, int H) { return vp_use(H) ? vp_groups(V) : (V + vt_c
 
 void launch_vocab_topk(const bf16* X, const bf16* WT, const float* bias, const float* pgen, const float* attn,
                        const int* ext, const int* lens, int* out_ids, float* out_lp, float* logits, float* part_ms,
-                       int R, int V, int H, int T, int K, int beam, PgIn pgi, hipStream_t st, const BeamTail* bt) {
+                       int R, int V, int H, int T, int K, int beam, PgIn pgi, hipStream_t st, const BeamTail* bt,
+                       const NgSeq* ng) {
   const int nt = vocab_topk_tiles(V, H);
   const BeamTail none{};
+  const bool ngram = bt && ng && ng->n > 1;  // (the stamp build of the select kernel is without it)
+  const NgSeq ngv = ngram ? *ng : NgSeq{};
   const bool span = vp_use(H);
   if (span) {
     const size_t lds = (size_t)vp_xrows(H, R) * (2 * H + 8 * VP_WAVES);
@@ -871,7 +880,10 @@ void launch_vocab_topk(const bf16* X, const bf16* WT, const float* bias, const f
     else if (H == 256) VPL(256);
     else VPL(512);
 #undef VPL
-    if (vs_stamp_host)
+    if (ngram)
+      hipLaunchKernelGGL((vocab_select_kernel<false, NgSeq>), dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms, pgen, attn,
+                         ext, lens, out_ids, out_lp, V, T, K, beam, nt, 16 * VP_NI * VP_WAVES, pgi, *bt, 1, ngv);
+    else if (vs_stamp_host)
       hipLaunchKernelGGL(vocab_select_kernel<true>, dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms, pgen, attn, ext, lens,
                          out_ids, out_lp, V, T, K, beam, nt, 16 * VP_NI * VP_WAVES, pgi, bt ? *bt : none, 1);
     else
@@ -894,6 +906,10 @@ void launch_vocab_topk(const bf16* X, const bf16* WT, const float* bias, const f
     hipLaunchKernelGGL((vocab_logits_kernel<2, 1, 512, true>), dim3(8 * RB * ((nt + 7) / 8)), dim3(256), 0, st, X, WT,
                        bias, logits, part_ms, R, V, H);
   }
-  hipLaunchKernelGGL(vocab_select_kernel<false>, dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms, pgen, attn, ext, lens,
-                     out_ids, out_lp, V, T, K, beam, nt, tcols, pgi, bt ? *bt : none, 0);
+  if (ngram)
+    hipLaunchKernelGGL((vocab_select_kernel<false, NgSeq>), dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms, pgen, attn,
+                       ext, lens, out_ids, out_lp, V, T, K, beam, nt, tcols, pgi, *bt, 0, ngv);
+  else
+    hipLaunchKernelGGL(vocab_select_kernel<false>, dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms, pgen, attn, ext, lens,
+                       out_ids, out_lp, V, T, K, beam, nt, tcols, pgi, bt ? *bt : none, 0);
 }

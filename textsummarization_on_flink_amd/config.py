@@ -68,6 +68,8 @@ class HParams:
     pad_enc_to_max: bool = True    # static shapes for hipGraph capture (padding is masked)
     graph: bool = True             # capture the train step / decode step in hipGraphs
     decode_batch: int = 64         # articles decoded together (beam-as-batch x articles)
+    block_ngram_repeat: int = 0    # beam search: a candidate that would repeat an n-gram of its hypothesis
+                                   # gets log-prob -1e20 (3 = trigram blocking; 0 / 1 = off)
     stream_max_wait_ms: float = 0.0   # streaming decode: queued requests always share a batch; after
                                       # the first, wait at most this long for more (0 = no waiting)
     save_model_secs: int = 60      # Supervisor(save_model_secs=60), run_summarization.py:199
@@ -173,6 +175,8 @@ def check_hps(hps: HParams) -> None:
     if hps.convert_to_coverage_model and not hps.coverage:
         raise ValueError("To convert your non-coverage model to a coverage model, run with "
                          "convert_to_coverage_model=True and coverage=True")  # :188
+    if hps.block_ngram_repeat < 0:
+        raise ValueError("block_ngram_repeat must be >= 0 (0 or 1 = off)")
 
 
 @dataclass

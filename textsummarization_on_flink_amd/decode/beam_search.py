@@ -11,6 +11,11 @@ Reproduced quirks:
     finished, the live hyps are used; the best by average log-prob is returned.
   * in-article OOV ids (>= vocab size) are fed back as [UNK].
 
+Not in the reference: ``hps.block_ngram_repeat = n`` (n >= 2) blocks repeated n-grams
+(``ngram_blocked``): a candidate that would complete an n-gram its hypothesis already contains
+keeps its place among the hypothesis' top 2*beam candidates, but its step log-prob becomes
+``BLOCKED_LP``, so it ranks behind every unblocked candidate (OpenNMT-py's block_ngram_repeat).
+
 The step model is pluggable (``StepModel``): the PyTorch oracle on CPU, or the gfx950
 decode step on GPU.  The batched device-resident version (many articles per launch,
 hipGraph-captured) lives in ``decode.device_beam``.
@@ -50,6 +55,21 @@ class Hypothesis:
     @property
     def avg_log_prob(self) -> float:
         return self.log_prob / len(self.tokens)
+
+
+BLOCKED_LP = -1e20  # step log-prob of a blocked candidate (fp32: lp_sum + BLOCKED_LP == BLOCKED_LP)
+
+
+def ngram_blocked(tokens, w: int, n: int) -> bool:
+    """Would appending ``w`` to ``tokens`` (the hypothesis' ids as chosen, [START] first, in-article
+    OOVs with their extended ids) repeat one of its n-grams?  True iff, with L = len(tokens),
+    L >= n and some p in [0, L - n] has tokens[p : p+n-1] == tokens[L-n+1 :] and
+    tokens[p+n-1] == w.  n <= 1 never blocks."""
+    L = len(tokens)
+    if n <= 1 or L < n:
+        return False
+    suffix = list(tokens[L - n + 1:])
+    return any(tokens[p + n - 1] == w and list(tokens[p:p + n - 1]) == suffix for p in range(L - n + 1))
 
 
 def sort_hyps(hyps: List[Hypothesis]) -> List[Hypothesis]:
@@ -99,6 +119,7 @@ def run_beam_search(model, vocab, batch, hps) -> Hypothesis:
     hyps = [Hypothesis([start], [0.0], dec_in_state, [], [], np.zeros([T], np.float32)) for _ in range(hps.beam_size)]
     results: List[Hypothesis] = []
     steps = 0
+    ngram = int(getattr(hps, "block_ngram_repeat", 0))
     while steps < hps.max_dec_steps and len(results) < hps.beam_size:
         latest = [h.latest_token if h.latest_token < V else unk for h in hyps]
         ids, lps, new_states, attn, pgens, covs = model.decode_onestep(
@@ -108,8 +129,10 @@ def run_beam_search(model, vocab, batch, hps) -> Hypothesis:
         num_orig = 1 if steps == 0 else len(hyps)
         for i in range(num_orig):
             for j in range(2 * hps.beam_size):
-                all_hyps.append(hyps[i].extend(int(ids[i, j]), float(lps[i, j]), new_states[i], attn[i], pgens[i],
-                                               covs[i]))
+                tok, lp = int(ids[i, j]), float(lps[i, j])
+                if ngram > 1 and ngram_blocked(hyps[i].tokens, tok, ngram):
+                    lp = BLOCKED_LP
+                all_hyps.append(hyps[i].extend(tok, lp, new_states[i], attn[i], pgens[i], covs[i]))
         hyps = []
         for h in sort_hyps(all_hyps):
             if h.latest_token == stop:

@@ -54,6 +54,12 @@ class DeviceBeamDecoder:
         self.V = vocab.size()
         self.maxD = hps.max_dec_steps
         self.use_graph, self.chunk, self.keep_attn = use_graph, chunk, keep_attn
+        # n-gram blocking (hps.block_ngram_repeat, semantics of beam_search.ngram_blocked) in the
+        # beam bookkeeping of both step variants; 0 = off (the kernels without it)
+        n = int(getattr(hps, "block_ngram_repeat", 0))
+        if n < 0:
+            raise ValueError("block_ngram_repeat must be >= 0")
+        self.ngram = n if n > 1 else 0
         # decode steps per captured graph: a whole early-exit chunk when it is even (one graph
         # launch per chunk instead of one per step pair), else 2
         self.gsteps = chunk if chunk % 2 == 0 else 2
@@ -136,6 +142,16 @@ class DeviceBeamDecoder:
         if self.keep_attn:
             b["ATT_hist"] = z(D, R, T)
             b["PG_hist"] = z(D, R)
+        # n-gram blocking: the hypotheses' token sequences, ping-pong like the decoder state --
+        # step t reads seq[t & 1][r][0..t] ([START] first) and writes seq[(t + 1) & 1] (the kernels
+        # take the parity from the device step counter, so a captured graph needs none)
+        self.seq = None
+        if self.ngram:
+            P = (D + 1 + 3) // 4 * 4
+            if self.beam * P > 4096:
+                raise ValueError(f"block_ngram_repeat: beam_size * (max_dec_steps + 1) = {self.beam * (D + 1)} "
+                                 "exceeds the 4096 tokens per article the beam kernels hold")
+            self.seq = [z(R, P, dt=torch.int32) for _ in range(2)]
         self.b = b
 
     def refresh_weights(self):
@@ -238,6 +254,9 @@ class DeviceBeamDecoder:
                   "art_ctr", "gran"):
             b[n].zero_()
         b["res_score"].fill_(-float("inf"))
+        if self.seq is not None:
+            self.seq[0].zero_()
+            self.seq[0][:, 0] = self.vocab.word2id(START_DECODING)
 
     def _attention(self, cov, att_out, ctx_out, ctx_bf):
         """a_t = softmax(e_t), ctx_t = sum_i a_ti E_i for all R hypotheses (coverage, if any,
@@ -291,11 +310,15 @@ class DeviceBeamDecoder:
         # beam bookkeeping; also appends a_t / p_gen to the histories (b["step"] was advanced by
         # this step's beam_gather: no grid-wide counter here)
         hist = self.keep_attn
-        k.beam_step(b["top_ids"], b["top_lp"], b["lp_sum"], b["latest"], b["gidx"], b["tok_hist"], b["par_hist"],
-                    b["done"], b["res_count"], b["res_score"], b["res_len"], b["res_step"], b["res_par"], b["step"],
-                    None, Y["ATT"] if hist else None, b["ATT_hist"] if hist else None,
-                    pg if (hist and pg is not None) else None, b["PG_hist"] if (hist and pg is not None) else None,
-                    T, self.Na, self.beam, K, self.vocab.word2id(STOP_DECODING), hps.min_dec_steps, self.maxD)
+        args = (b["top_ids"], b["top_lp"], b["lp_sum"], b["latest"], b["gidx"], b["tok_hist"], b["par_hist"],
+                b["done"], b["res_count"], b["res_score"], b["res_len"], b["res_step"], b["res_par"], b["step"],
+                None, Y["ATT"] if hist else None, b["ATT_hist"] if hist else None,
+                pg if (hist and pg is not None) else None, b["PG_hist"] if (hist and pg is not None) else None,
+                T, self.Na, self.beam, K, self.vocab.word2id(STOP_DECODING), hps.min_dec_steps, self.maxD)
+        if self.ngram:
+            k.beam_step_ng(*args, self.seq[0], self.seq[1], self.ngram)
+        else:
+            k.beam_step(*args)
 
     def _step_fused(self, parity: int):
         """One decode step in 6 launches (reference model.py:367-443 decode_onestep + the beam
@@ -319,15 +342,19 @@ class DeviceBeamDecoder:
                             Y["ATT"], Y["CTX"], Y["CTXb"], R, T, A, self.rep)
         k.linear2(Y["H"], H, Y["CTXb"], A, eng.pk["OUTmT"], p[OUT_B], None, None, b["outb"], R, H)
         ptr, hist = hps.pointer_gen, self.keep_attn
-        k.vocab_topk_beam(b["outb"], self.owT, p[OV], Y["CTX"] if ptr else None, Y["C"] if ptr else None,
-                          Y["H"] if ptr else None, b["x"] if ptr else None, self.pg_w if ptr else None,
-                          p[PG_B] if ptr else None, b["PG"] if ptr else None, Y["ATT"] if (ptr or hist) else None,
-                          b["ext"], b["lens"], b["top_ids"], b["top_lp"], b["logits"], b["vpart_ms"], b["lp_sum"],
-                          b["latest"], b["gidx"], b["tok_hist"], b["par_hist"], b["done"], b["res_count"],
-                          b["res_score"], b["res_len"], b["res_step"], b["res_par"], b["step"], b["art_ctr"],
-                          b["gran"], b["tail_err"],
-                          b["ATT_hist"] if hist else None, b["PG_hist"] if (hist and ptr) else None, R, V, H, T, K,
-                          self.beam, A, E, self.vocab.word2id(STOP_DECODING), hps.min_dec_steps, self.maxD)
+        args = (b["outb"], self.owT, p[OV], Y["CTX"] if ptr else None, Y["C"] if ptr else None,
+                Y["H"] if ptr else None, b["x"] if ptr else None, self.pg_w if ptr else None,
+                p[PG_B] if ptr else None, b["PG"] if ptr else None, Y["ATT"] if (ptr or hist) else None,
+                b["ext"], b["lens"], b["top_ids"], b["top_lp"], b["logits"], b["vpart_ms"], b["lp_sum"],
+                b["latest"], b["gidx"], b["tok_hist"], b["par_hist"], b["done"], b["res_count"],
+                b["res_score"], b["res_len"], b["res_step"], b["res_par"], b["step"], b["art_ctr"],
+                b["gran"], b["tail_err"],
+                b["ATT_hist"] if hist else None, b["PG_hist"] if (hist and ptr) else None, R, V, H, T, K,
+                self.beam, A, E, self.vocab.word2id(STOP_DECODING), hps.min_dec_steps, self.maxD)
+        if self.ngram:
+            k.vocab_topk_beam_ng(*args, self.seq[0], self.seq[1], self.ngram)
+        else:
+            k.vocab_topk_beam(*args)
 
     @staticmethod
     def _check_tail(err: int) -> None:
