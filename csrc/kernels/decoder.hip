@@ -360,12 +360,16 @@ __global__ __launch_bounds__(256) void dec_bwd_dz_kernel(
   xcd_tile(tx, ty);
   const int n0 = tx * 16, r0 = ty * 16;
   if (n0 >= E + H && !dctx_prev_out) return;  // uniform per block
-  if (tile_dead(dlen, step, r0, B)) {  // every output is an exact zero past the last live step
+  if (tile_dead(dlen, step, r0, B)) {  // dz_t == 0: dx_t and dh_rec are exact zeros past the last live step;
+    // dctx_{t-1} belongs to step t - 1, which is still live for a row with dlen == t: it keeps its direct term
     const int r = r0 + (lane >> 4) * 4 + wid, n = n0 + (lane & 15);
     if (r < B) {
       if (n < E) dx_out[(size_t)r * E + n] = 0.f;
       else if (n < E + H) dh_rec[(size_t)r * H + n - E] = 0.f;
-      else dctx_prev_out[(size_t)r * A + n - E - H] = 0.f;
+      else {
+        const size_t ia = (size_t)r * A + n - E - H;
+        dctx_prev_out[ia] = dCTX_dir_prev ? dCTX_dir_prev[ia] : 0.f;
+      }
     }
     return;
   }

@@ -8,7 +8,8 @@ persistent launch with per-tile hand-offs, against
   per-kernel tests: the attention outputs 2e-3 of the largest reference magnitude (fp32) and 1e-2
   (bf16), as test_gpu_attention_ops applies to attn_fwd_rowp; S an absolute error below
   1e-3 max|ref| + 1e-4, as test_gpu_decode.py::test_linear2_matches_fp32 applies to linear2.  The
-  cell has no per-kernel test of its own: its fp32-accumulated bf16 MFMA sums and v_exp / v_rcp
+  cell (dec_cell_fwd) and dec_sproj are checked on their own against float64 in
+  test_gpu_decoder_ops.py; here the cell's fp32-accumulated bf16 MFMA sums and v_exp / v_rcp
   activations are held to the attention's bounds.
 
 Shapes: H = 256, E = 128, A = 512, D = 4, T = 24; B = 16 (one team), 48 (three teams: not a multiple
