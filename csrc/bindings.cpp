@@ -223,6 +223,17 @@ bool dec_persistent_ok_op(int64_t H, int64_t E, int64_t A, int64_t B, int64_t T)
 int64_t dec_persistent_grid_op(int64_t B) { return dec_persistent_grid((int)B); }
 int64_t dec_persistent_capacity_op() { return dec_persistent_capacity(); }
 int64_t dec_persistent_xbuf_op(int64_t B) { return (int64_t)dec_persistent_xbuf_elems((int)B); }
+// clock stamps of later dec_fwd_persistent launches into buf ([grid][D][8] int32; None: stop); only a
+// library built with -DTSAMD_DEC_STAMPS has them (tools/dec_persistent_stamps.py)
+int64_t dec_persistent_stamps_op(const OT& buf, int64_t B, int64_t D) {
+  if (buf.has_value()) {
+    chk(*buf, I32, "stamps");
+    TORCH_CHECK(buf->numel() >= dec_persistent_grid((int)B) * D * 8, "stamps too small");
+  }
+  const int n = dec_persistent_stamps_into(buf.has_value() ? (unsigned*)buf->data_ptr() : nullptr);
+  TORCH_CHECK(n > 0, "dec_persistent_stamps: this library was built without -DTSAMD_DEC_STAMPS");
+  return n;
+}
 void dec_fwd_persistent(const Tensor& XG, const Tensor& KcT, const Tensor& WsT, const Tensor& bs, const Tensor& Cst,
                         const Tensor& Cb, const Tensor& Hb, const Tensor& ACT, const Tensor& S, const Tensor& F,
                         const Tensor& G, const Tensor& v, const OT& wc, const OT& COV, const Tensor& lens,
@@ -1273,6 +1284,7 @@ TORCH_LIBRARY(tsamd, m) {
   m.def("dec_persistent_grid", &dec_persistent_grid_op);
   m.def("dec_persistent_capacity", &dec_persistent_capacity_op);
   m.def("dec_persistent_xbuf", &dec_persistent_xbuf_op);
+  m.def("dec_persistent_stamps", &dec_persistent_stamps_op);
   m.def("dec_fwd_persistent", &dec_fwd_persistent);
   m.def("attn_bwd_rowp", &attn_bwd_rowp);
   m.def("attn_bwd_feat", &attn_bwd_feat);

@@ -14,7 +14,7 @@ namespace handoff {
 
 typedef __attribute__((address_space(1))) unsigned long long gu64;
 typedef __attribute__((address_space(1))) unsigned int gu32;
-// a sweep gives up after kSpinLimit / 4 passes with s_sleep(24) between them: ~0.1-1 s
+// a sweep gives up after kSpinLimit / 4 passes with s_sleep(SLEEP) between them: ~0.1-1 s at 24
 constexpr unsigned kSpinLimit = 1u << 21;
 
 __device__ __forceinline__ unsigned pack_bf2(float lo, float hi) {
@@ -28,8 +28,9 @@ __device__ __forceinline__ void store_granule(gu64* g, unsigned tag, unsigned v)
 }
 
 // One wave reads NPL granules per lane (indices first + j*64 + lane) until every tag
-// matches; a pass re-reads only the granules that were not ready yet.
-template <int NPL>
+// matches; a pass re-reads only the granules that were not ready yet.  SLEEP: the s_sleep argument
+// between passes (64 clocks each), a per-kernel choice.
+template <int NPL, int SLEEP = 24>
 __device__ __forceinline__ void sweep(const gu64* g, int first, unsigned tag, unsigned (&v)[NPL], bool& dead,
                                       gu32* err, unsigned code, int lane) {
   static_assert(NPL <= 32, "ready mask is 32 bits");
@@ -53,12 +54,12 @@ __device__ __forceinline__ void sweep(const gu64* g, int first, unsigned tag, un
       dead = true;
       return;
     }
-    // s_sleep(24) (~1500 clocks) between passes: the polls of 32 teams are a large share of
+    // The LSTM's s_sleep(24) (~1500 clocks) between passes: the polls of 32 teams are a large share of
     // the L2 traffic, and fewer of them lower every team's hand-off latency (tools/lstm_micro.py,
     // per step: H = 512, B = 256: 6.82 us with s_sleep(1), 6.65 with 8, 6.28 with 24, 6.27 with
     // 48; H = 256, B = 256: 3.01 / 2.97 / 2.97 / 3.46).  Spinning on one granule per lane first
     // and sweeping once it is ready costs one more L2 round trip: 6.8 -> 8.3 us.
-    __builtin_amdgcn_s_sleep(24);
+    __builtin_amdgcn_s_sleep(SLEEP);
   }
 }
 

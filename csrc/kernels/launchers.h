@@ -63,6 +63,7 @@ bool dec_persistent_shape_ok(int H, int E, int A, int B, int T);
 int dec_persistent_grid(int B);
 int dec_persistent_capacity();
 size_t dec_persistent_xbuf_elems(int B);
+int dec_persistent_stamps_into(unsigned* buf);
 void launch_dec_fwd_persistent(const float* XG, const bf16* KcT, const bf16* WsT, const float* bs, float* Cst, bf16* Cb,
                                bf16* Hb, float* ACT, float* S, const bf16* F, const bf16* G, const float* v,
                                const float* wc, float* COV, const int* lens, float* ATT, bf16* ATTb, float* covloss,

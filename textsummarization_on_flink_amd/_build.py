@@ -75,6 +75,15 @@ def _headers(d):
     return out
 
 
+def kernel_flags(debug=False):
+    """The hipcc flags every csrc/kernels/*.hip is compiled with."""
+    flags = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contract=fast",
+             "-Wno-unused-result", "-munsafe-fp-atomics", f"-I{os.path.join(CSRC, 'kernels')}"]
+    if debug:
+        flags += ["-DTSAMD_DEBUG", "-fgpu-rdc"]
+    return flags
+
+
 def build_kernels(verbose=False, jobs=8, debug=False):
     """Compile csrc/kernels/*.hip + csrc/bindings.cpp into textsummarization_on_flink_amd/_C.so.
 
@@ -86,10 +95,7 @@ def build_kernels(verbose=False, jobs=8, debug=False):
     kdir = os.path.join(CSRC, "kernels")
     hips = sorted(os.path.join(kdir, f) for f in os.listdir(kdir) if f.endswith(".hip"))
     hdrs = _headers(kdir)
-    common = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contract=fast",
-              "-Wno-unused-result", "-munsafe-fp-atomics", f"-I{kdir}"]
-    if debug:
-        common += ["-DTSAMD_DEBUG", "-fgpu-rdc"]
+    common = kernel_flags(debug)
     objs, jobsl = [], []
     for src in hips:
         obj = os.path.join(bdir, os.path.basename(src) + ".o")
