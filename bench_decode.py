@@ -34,6 +34,10 @@ def main():
                     help="A/B: the 8-launch decode step (separate beam_step) instead of the fused beam tail")
     ap.add_argument("--block_ngram_repeat", type=int, default=0,
                     help="n-gram blocking in the beam bookkeeping (3 = trigram blocking; 0 = off)")
+    ap.add_argument("--length_penalty", default="avg", help="avg (the reference) | wu | none")
+    ap.add_argument("--length_alpha", type=float, default=0.9)
+    ap.add_argument("--coverage_penalty_beta", type=float, default=0.0,
+                    help="summary coverage penalty in the beam bookkeeping (0 = off)")
     args = ap.parse_args()
     import torch
     from textsummarization_on_flink_amd.config import HParams
@@ -43,7 +47,8 @@ def main():
 
     hps = HParams(mode="decode", batch_size=args.articles, beam_size=args.beam, coverage=True, vocab_size=args.vocab,
                   hidden_dim=args.hidden, enc_layers=args.layers, max_enc_steps=args.enc,
-                  block_ngram_repeat=args.block_ngram_repeat)
+                  block_ngram_repeat=args.block_ngram_repeat, length_penalty=args.length_penalty,
+                  length_alpha=args.length_alpha, coverage_penalty_beta=args.coverage_penalty_beta)
     corpus = SyntheticCorpus(vocab_size=args.vocab, seed=7)
     vocab = corpus.vocab(args.vocab)
     batches = make_batches(hps, vocab, corpus, args.batches + args.warmup, pad_enc_to=hps.max_enc_steps)
@@ -87,7 +92,9 @@ def main():
                                  "beam": args.beam, "articles_per_batch": args.articles,
                                  "rows": args.articles * args.beam, "graph": not args.no_graph,
                                  "pipelined": args.pipelined, "fused_step": bool(dec.fused_step),
-                                 "block_ngram_repeat": args.block_ngram_repeat}}))
+                                 "block_ngram_repeat": args.block_ngram_repeat,
+                                 "length_penalty": args.length_penalty, "length_alpha": args.length_alpha,
+                                 "coverage_penalty_beta": args.coverage_penalty_beta}}))
 
 
 if __name__ == "__main__":

@@ -986,11 +986,39 @@ NgSeq ng_seq(const OT& seq0, const OT& seq1, int64_t ngram, int64_t R, int64_t b
   return NgSeq{{P<int>(*seq0), P<int>(*seq1)}, (int)pitch, (int)ngram};
 }
 
+// Length / coverage penalties of the beam bookkeeping (BeamPen, launchers.h): inv_len fp32
+// [>= max_dec + 2], cpen fp32 [R] (optional: no coverage penalty), key_sum / res_lp fp32 [R].
+BeamPen beam_pen(const Tensor& inv_len, const OT& cpen, double beta, const Tensor& key_sum, const Tensor& res_lp,
+                 int64_t R, int64_t max_dec) {
+  chk(inv_len, F32, "inv_len"); chk(key_sum, F32, "key_sum"); chk(res_lp, F32, "res_lp");
+  TORCH_CHECK(inv_len.numel() >= max_dec + 2, "inv_len needs max_dec + 2 entries");
+  numel_eq(key_sum, R, "key_sum"); numel_eq(res_lp, R, "res_lp"); chko(cpen, F32, R, "cpen");
+  TORCH_CHECK(beta >= 0, "beta must be >= 0");
+  return BeamPen{P<float>(inv_len), PO<float>(cpen), (float)beta, P<float>(key_sum), P<float>(res_lp)};
+}
+
+// cpen[r] = sum_{i < lens[r / beam]} max(cov[r][i] + att[r][i] - 1, 0) (the summary coverage penalty);
+// a0 (optional, fp32 [R / beam][T]): subtracted from cov, per article
+void cov_penalty(const Tensor& cov, const Tensor& att, const Tensor& lens, const Tensor& cpen, int64_t R, int64_t T,
+                 int64_t beam, const OT& a0) {
+  chk(cov, F32, "cov"); chk(att, F32, "att"); chk(lens, I32, "lens"); chk(cpen, F32, "cpen");
+  TORCH_CHECK(R >= 1 && T >= 1 && beam >= 1 && R % beam == 0, "bad cov_penalty args");
+  numel_eq(cov, R * T, "cov"); numel_eq(att, R * T, "att"); numel_eq(lens, R / beam, "lens");
+  TORCH_CHECK(cpen.numel() >= R, "cpen too small");
+  TORCH_CHECK(T % 4 != 0 || ((uintptr_t)cov.data_ptr() % 16 == 0 && (uintptr_t)att.data_ptr() % 16 == 0),
+              "cov / att must be 16-byte aligned");
+  chko(a0, F32, R / beam * T, "a0");
+  TORCH_CHECK(T % 4 != 0 || !PO<float>(a0) || (uintptr_t)PO<float>(a0) % 16 == 0, "a0 must be 16-byte aligned");
+  launch_cov_penalty(P<float>(cov), P<float>(att), P<int>(lens), P<float>(cpen), (int)R, (int)T, (int)beam, stream(),
+                     PO<float>(a0));
+}
+
 // One beam-decode step's head: vocab_topk (p_gen inside when the pointer inputs are given) with
 // the beam bookkeeping fused into the select kernel's per-article tail (replaces vocab_topk_pg +
 // beam_step).  The step counter was advanced at the start of the step (dec_cell_fwd_beam).
 // seq0 / seq1 / ngram: n-gram blocking (see ng_seq), off for ngram <= 1.
-void vocab_topk_beam_ng(const Tensor& X, const Tensor& WT, const Tensor& bias, const OT& ctx, const OT& c, const OT& h,
+// pen (optional): length / coverage penalties (see beam_pen).
+static void vocab_topk_beam_run(const Tensor& X, const Tensor& WT, const Tensor& bias, const OT& ctx, const OT& c, const OT& h,
                      const OT& x, const OT& pg_w, const OT& pg_b, const OT& pg_out, const OT& attn, const Tensor& ext,
                      const Tensor& lens, const Tensor& out_ids, const Tensor& out_lp, const Tensor& logits,
                      const Tensor& part_ms, const Tensor& lp_sum, const Tensor& latest, const Tensor& gidx,
@@ -999,7 +1027,8 @@ void vocab_topk_beam_ng(const Tensor& X, const Tensor& WT, const Tensor& bias, c
                      const Tensor& step, const Tensor& art_ctr, const Tensor& gran, const Tensor& err,
                      const OT& att_hist, const OT& pg_hist, int64_t R,
                      int64_t V, int64_t H, int64_t T, int64_t K, int64_t beam, int64_t A, int64_t E, int64_t stop_id,
-                     int64_t min_dec, int64_t max_dec, const OT& seq0, const OT& seq1, int64_t ngram) {
+                     int64_t min_dec, int64_t max_dec, const OT& seq0, const OT& seq1, int64_t ngram,
+                     const BeamPen* pen) {
   chk(X, BF, "X"); chk(WT, BF, "WT"); chk(bias, F32, "bias"); chk(ext, I32, "ext"); chk(lens, I32, "lens");
   chk(out_ids, I32, "out_ids"); chk(out_lp, F32, "out_lp"); chk(logits, F32, "logits"); chk(part_ms, F32, "part_ms");
   const int64_t nt = vocab_topk_tiles((int)V, (int)H), Na = R / beam;
@@ -1041,7 +1070,43 @@ void vocab_topk_beam_ng(const Tensor& X, const Tensor& WT, const Tensor& bias, c
   const NgSeq ng = ng_seq(seq0, seq1, ngram, R, beam, max_dec);
   launch_vocab_topk(P<bf16>(X), P<bf16>(WT), P<float>(bias), nullptr, ptr ? PO<float>(attn) : nullptr, P<int>(ext),
                     P<int>(lens), P<int>(out_ids), P<float>(out_lp), P<float>(logits), P<float>(part_ms), R, V, H, T, K,
-                    beam, pgi, stream(), &bt, &ng);
+                    beam, pgi, stream(), &bt, &ng, pen);
+}
+
+void vocab_topk_beam_ng(const Tensor& X, const Tensor& WT, const Tensor& bias, const OT& ctx, const OT& c, const OT& h,
+                     const OT& x, const OT& pg_w, const OT& pg_b, const OT& pg_out, const OT& attn, const Tensor& ext,
+                     const Tensor& lens, const Tensor& out_ids, const Tensor& out_lp, const Tensor& logits,
+                     const Tensor& part_ms, const Tensor& lp_sum, const Tensor& latest, const Tensor& gidx,
+                     const Tensor& tok_hist, const Tensor& par_hist, const Tensor& done, const Tensor& res_count,
+                     const Tensor& res_score, const Tensor& res_len, const Tensor& res_step, const Tensor& res_par,
+                     const Tensor& step, const Tensor& art_ctr, const Tensor& gran, const Tensor& err,
+                     const OT& att_hist, const OT& pg_hist, int64_t R,
+                     int64_t V, int64_t H, int64_t T, int64_t K, int64_t beam, int64_t A, int64_t E, int64_t stop_id,
+                     int64_t min_dec, int64_t max_dec, const OT& seq0, const OT& seq1, int64_t ngram) {
+  vocab_topk_beam_run(X, WT, bias, ctx, c, h, x, pg_w, pg_b, pg_out, attn, ext, lens, out_ids, out_lp, logits, part_ms,
+                      lp_sum, latest, gidx, tok_hist, par_hist, done, res_count, res_score, res_len, res_step, res_par,
+                      step, art_ctr, gran, err, att_hist, pg_hist, R, V, H, T, K, beam, A, E, stop_id, min_dec, max_dec,
+                      seq0, seq1, ngram, nullptr);
+}
+
+// vocab_topk_beam_ng with the length / coverage penalties (ngram = 0 or no seq: penalties only)
+void vocab_topk_beam_pen(const Tensor& X, const Tensor& WT, const Tensor& bias, const OT& ctx, const OT& c, const OT& h,
+                     const OT& x, const OT& pg_w, const OT& pg_b, const OT& pg_out, const OT& attn, const Tensor& ext,
+                     const Tensor& lens, const Tensor& out_ids, const Tensor& out_lp, const Tensor& logits,
+                     const Tensor& part_ms, const Tensor& lp_sum, const Tensor& latest, const Tensor& gidx,
+                     const Tensor& tok_hist, const Tensor& par_hist, const Tensor& done, const Tensor& res_count,
+                     const Tensor& res_score, const Tensor& res_len, const Tensor& res_step, const Tensor& res_par,
+                     const Tensor& step, const Tensor& art_ctr, const Tensor& gran, const Tensor& err,
+                     const OT& att_hist, const OT& pg_hist, int64_t R,
+                     int64_t V, int64_t H, int64_t T, int64_t K, int64_t beam, int64_t A, int64_t E, int64_t stop_id,
+                     int64_t min_dec, int64_t max_dec, const OT& seq0, const OT& seq1, int64_t ngram,
+                     const Tensor& inv_len, const OT& cpen, double beta, const Tensor& key_sum, const Tensor& res_lp) {
+  const BeamPen pen = beam_pen(inv_len, cpen, beta, key_sum, res_lp, R, max_dec);
+  const bool ng = ngram > 1 && seq0.has_value() && seq0->defined();
+  vocab_topk_beam_run(X, WT, bias, ctx, c, h, x, pg_w, pg_b, pg_out, attn, ext, lens, out_ids, out_lp, logits, part_ms,
+                      lp_sum, latest, gidx, tok_hist, par_hist, done, res_count, res_score, res_len, res_step, res_par,
+                      step, art_ctr, gran, err, att_hist, pg_hist, R, V, H, T, K, beam, A, E, stop_id, min_dec, max_dec,
+                      seq0, seq1, ng ? ngram : 0, &pen);
 }
 
 void vocab_topk_beam(const Tensor& X, const Tensor& WT, const Tensor& bias, const OT& ctx, const OT& c, const OT& h,
@@ -1124,12 +1189,13 @@ void attn_fwd_row_beam(const Tensor& F, const Tensor& E, const Tensor& s, const 
 // is given; without ctr, beam_gather advanced it at the start of the decode step (t = step - 1).
 // att/att_hist/pg/pg_hist (optional): this step's attention rows and p_gen copied into row
 // min(step, max_dec - 1) of the histories.  seq0 / seq1 / ngram: n-gram blocking (see ng_seq).
-void beam_step_ng(const Tensor& top_ids, const Tensor& top_lp, const Tensor& lp_sum, const Tensor& latest,
+// pen (optional): length / coverage penalties (see beam_pen).
+static void beam_step_run(const Tensor& top_ids, const Tensor& top_lp, const Tensor& lp_sum, const Tensor& latest,
                const Tensor& gidx, const Tensor& tok_hist, const Tensor& par_hist, const Tensor& done,
                const Tensor& res_count, const Tensor& res_score, const Tensor& res_len, const Tensor& res_step,
                const Tensor& res_par, const Tensor& step, const OT& ctr, const OT& att, const OT& att_hist,
                const OT& pg, const OT& pg_hist, int64_t T, int64_t Na, int64_t beam, int64_t K, int64_t stop_id,
-               int64_t min_dec, int64_t max_dec, const OT& seq0, const OT& seq1, int64_t ngram) {
+               int64_t min_dec, int64_t max_dec, const OT& seq0, const OT& seq1, int64_t ngram, const BeamPen* pen) {
   chk(top_ids, I32, "top_ids"); chk(top_lp, F32, "top_lp"); chk(lp_sum, F32, "lp_sum"); chk(latest, I32, "latest");
   chk(gidx, I32, "gidx"); chk(tok_hist, I32, "tok_hist"); chk(par_hist, I32, "par_hist"); chk(done, I32, "done");
   chk(res_count, I32, "res_count"); chk(res_score, F32, "res_score"); chk(res_len, I32, "res_len");
@@ -1150,7 +1216,33 @@ void beam_step_ng(const Tensor& top_ids, const Tensor& top_lp, const Tensor& lp_
                    P<int>(par_hist), P<int>(done), P<int>(res_count), P<float>(res_score), P<int>(res_len),
                    P<int>(res_step), P<int>(res_par), P<int>(step), (unsigned*)PO<int>(ctr), PO<float>(att),
                    PO<float>(att_hist), PO<float>(pg), PO<float>(pg_hist), (int)T, Na, beam, K, stop_id, min_dec,
-                   max_dec, stream(), &ng);
+                   max_dec, stream(), &ng, pen);
+}
+
+void beam_step_ng(const Tensor& top_ids, const Tensor& top_lp, const Tensor& lp_sum, const Tensor& latest,
+               const Tensor& gidx, const Tensor& tok_hist, const Tensor& par_hist, const Tensor& done,
+               const Tensor& res_count, const Tensor& res_score, const Tensor& res_len, const Tensor& res_step,
+               const Tensor& res_par, const Tensor& step, const OT& ctr, const OT& att, const OT& att_hist,
+               const OT& pg, const OT& pg_hist, int64_t T, int64_t Na, int64_t beam, int64_t K, int64_t stop_id,
+               int64_t min_dec, int64_t max_dec, const OT& seq0, const OT& seq1, int64_t ngram) {
+  beam_step_run(top_ids, top_lp, lp_sum, latest, gidx, tok_hist, par_hist, done, res_count, res_score, res_len, res_step,
+                res_par, step, ctr, att, att_hist, pg, pg_hist, T, Na, beam, K, stop_id, min_dec, max_dec, seq0, seq1,
+                ngram, nullptr);
+}
+
+// beam_step_ng with the length / coverage penalties (ngram = 0 or no seq: penalties only)
+void beam_step_pen(const Tensor& top_ids, const Tensor& top_lp, const Tensor& lp_sum, const Tensor& latest,
+               const Tensor& gidx, const Tensor& tok_hist, const Tensor& par_hist, const Tensor& done,
+               const Tensor& res_count, const Tensor& res_score, const Tensor& res_len, const Tensor& res_step,
+               const Tensor& res_par, const Tensor& step, const OT& ctr, const OT& att, const OT& att_hist,
+               const OT& pg, const OT& pg_hist, int64_t T, int64_t Na, int64_t beam, int64_t K, int64_t stop_id,
+               int64_t min_dec, int64_t max_dec, const OT& seq0, const OT& seq1, int64_t ngram,
+               const Tensor& inv_len, const OT& cpen, double beta, const Tensor& key_sum, const Tensor& res_lp) {
+  const BeamPen pen = beam_pen(inv_len, cpen, beta, key_sum, res_lp, Na * beam, max_dec);
+  const bool ng = ngram > 1 && seq0.has_value() && seq0->defined();
+  beam_step_run(top_ids, top_lp, lp_sum, latest, gidx, tok_hist, par_hist, done, res_count, res_score, res_len, res_step,
+                res_par, step, ctr, att, att_hist, pg, pg_hist, T, Na, beam, K, stop_id, min_dec, max_dec, seq0, seq1,
+                ng ? ngram : 0, &pen);
 }
 
 void beam_step(const Tensor& top_ids, const Tensor& top_lp, const Tensor& lp_sum, const Tensor& latest,
@@ -1339,6 +1431,8 @@ TORCH_LIBRARY(tsamd, m) {
   m.def("topk_parts", &topk_parts);
   m.def("beam_step", &beam_step);
   m.def("beam_step_ng", &beam_step_ng);
+  m.def("beam_step_pen", &beam_step_pen);
+  m.def("cov_penalty", &cov_penalty);
   m.def("beam_gather", &beam_gather);
   m.def("linear2", &linear2);
   m.def("pgen", &pgen);
@@ -1350,6 +1444,7 @@ TORCH_LIBRARY(tsamd, m) {
   m.def("lstm_bwd_stamps", &lstm_bwd_stamps);
   m.def("vocab_topk_beam", &vocab_topk_beam);
   m.def("vocab_topk_beam_ng", &vocab_topk_beam_ng);
+  m.def("vocab_topk_beam_pen", &vocab_topk_beam_pen);
   m.def("dec_cell_fwd_beam", &dec_cell_fwd_beam);
   m.def("beam_sproj_xmerge", &beam_sproj_xmerge);
   m.def("attn_fwd_row_beam", &attn_fwd_row_beam);

@@ -266,7 +266,8 @@ __global__ __launch_bounds__(TOPK_THREADS) void final_topk_merge_kernel(
 
 // n-gram blocking (beam_common.h): instantiated with one trailing NgSeq argument -- the
 // hypotheses' token sequences, parity from t; without it the kernel and its arguments are
-// exactly the plain bookkeeping
+// exactly the plain bookkeeping.  Length / coverage penalties: one trailing BeamPen argument
+// (after the NgSeq, if any), compiled in the same way.
 template <typename... NGA>
 __global__ __launch_bounds__(64) void beam_step_kernel(
     const int* __restrict__ top_ids, const float* __restrict__ top_lp,  // [R][K]
@@ -281,11 +282,12 @@ __global__ __launch_bounds__(64) void beam_step_kernel(
     const float* __restrict__ att, float* __restrict__ att_hist,  // optional: [R][T] -> [maxD][R][T]
     const float* __restrict__ pg, float* __restrict__ pg_hist,    // optional: [R] -> [maxD][R]
     int T, int beam, int K, int stop_id, int min_dec, int max_dec, NGA... nga) {
-  constexpr bool NG = sizeof...(NGA) == 1;
+  constexpr bool NG = pack_has<NgSeq, NGA...>, PEN = pack_has<BeamPen, NGA...>;
   const NgSeq ng = ng_of(nga...);
   __shared__ float cval[64];
   __shared__ int cid[64];
   __shared__ int srt[64];
+  __shared__ float ckey[PEN ? 64 : 1];
   __shared__ __attribute__((aligned(16))) int ban[NG ? NG_BAN_MAX : 4];
   __shared__ int adv_par[NG ? BEAM_CAND_MAX : 1], adv_tok[NG ? BEAM_CAND_MAX : 1];
   const int a = blockIdx.x, lane = threadIdx.x;
@@ -318,9 +320,9 @@ __global__ __launch_bounds__(64) void beam_step_kernel(
       __syncthreads();
       if (lane < beam * K && ngram_banned(ban, lane / K, ng.P, t, tid_cand)) tot = lps + BLOCKED_LP;
     }
-    beam_step_body<NG>(top_ids, top_lp, lp_sum, latest, gidx, tok_hist, par_hist, done, res_count, res_score, res_len,
-                       res_step, res_par, cval, cid, srt, a, lane, t, base, beam, K, stop_id, min_dec, tot, tid_cand,
-                       nres0, (int)gridDim.x, adv_par, adv_tok);
+    beam_step_body<NG, PEN>(top_ids, top_lp, lp_sum, latest, gidx, tok_hist, par_hist, done, res_count, res_score,
+                            res_len, res_step, res_par, cval, cid, srt, a, lane, t, base, beam, K, stop_id, min_dec, tot,
+                            tid_cand, nres0, (int)gridDim.x, adv_par, adv_tok, pen_of(nga...), ckey);
     if constexpr (NG) {
       __syncthreads();  // adv_par / adv_tok written by lanes < beam
       ngram_seq_advance(ng.seq[t & 1], ng.seq[(t + 1) & 1], adv_par, adv_tok, base, beam, ng.P, t, (int)R);
@@ -336,6 +338,47 @@ __global__ __launch_bounds__(64) void beam_step_kernel(
       *ctr = 0u;
     }
   }
+}
+
+// ------------------------------------------------------------------ coverage penalty
+// cpen[r] = sum_{i < lens[r / beam]} max(cov[r][i] + att[r][i] - 1, 0): the summary coverage
+// penalty of hypothesis row r with this step's attention included (cov: the steps before it).
+// a0 (optional, [R / beam][T]): subtracted from cov -- the decoder's coverage also holds the
+// initial-state attention of step 0 (reference attention_decoder.py:138-158), which is no step of
+// the hypothesis.
+// One wave per row, 4 rows per workgroup; 16-byte loads when the rows are 16-byte aligned
+// (T % 4 == 0); the wave sum stays in registers (DPP row sum, then the two permlane swaps).
+#define CP_ROWS 4
+__global__ __launch_bounds__(64 * CP_ROWS) void cov_penalty_kernel(
+    const float* __restrict__ cov, const float* __restrict__ att, const int* __restrict__ lens,
+    float* __restrict__ cpen, int R, int T, int beam, const float* __restrict__ a0) {
+  const int r = blockIdx.x * CP_ROWS + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (r >= R) return;  // whole waves: no barrier below
+  const int len = min(max(lens[r / beam], 0), T);
+  const float* c = cov + (size_t)r * T;
+  const float* a = att + (size_t)r * T;
+  const float* z = a0 ? a0 + (size_t)(r / beam) * T : nullptr;
+  float s = 0.f;
+  if ((T & 3) == 0) {
+    for (int i = lane * 4; i < len; i += 256) {  // i + 3 < T: T is a multiple of 4
+      const float4 cv = *reinterpret_cast<const float4*>(c + i), av = *reinterpret_cast<const float4*>(a + i);
+      const float4 zv = z ? *reinterpret_cast<const float4*>(z + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+      s += fmaxf(cv.x + av.x - zv.x - 1.f, 0.f);
+      if (i + 1 < len) s += fmaxf(cv.y + av.y - zv.y - 1.f, 0.f);
+      if (i + 2 < len) s += fmaxf(cv.z + av.z - zv.z - 1.f, 0.f);
+      if (i + 3 < len) s += fmaxf(cv.w + av.w - zv.w - 1.f, 0.f);
+    }
+  } else {
+    for (int i = lane; i < len; i += 64) s += fmaxf(c[i] + a[i] - (z ? z[i] : 0.f) - 1.f, 0.f);
+  }
+  s = sum_x32(sum_x16(dpp_sum16(s)));
+  if (lane == 0) cpen[r] = s;
+}
+
+void launch_cov_penalty(const float* cov, const float* att, const int* lens, float* cpen, int R, int T, int beam,
+                        hipStream_t st, const float* a0) {
+  hipLaunchKernelGGL(cov_penalty_kernel, dim3((R + CP_ROWS - 1) / CP_ROWS), dim3(64 * CP_ROWS), 0, st, cov, att, lens,
+                     cpen, R, T, beam, a0);
 }
 
 // ------------------------------------------------------------------ state gather
@@ -402,8 +445,17 @@ void launch_beam_step(const int* top_ids, const float* top_lp, float* lp_sum, in
                       int* par_hist, int* done, int* res_count, float* res_score, int* res_len, int* res_step,
                       int* res_par, int* step, unsigned* ctr, const float* att, float* att_hist, const float* pg,
                       float* pg_hist, int T, int Na, int beam, int K, int stop_id, int min_dec, int max_dec,
-                      hipStream_t st, const NgSeq* ng) {
-  if (ng && ng->n > 1)
+                      hipStream_t st, const NgSeq* ng, const BeamPen* pen) {
+  const bool ngram = ng && ng->n > 1;
+  if (pen && ngram)
+    hipLaunchKernelGGL((beam_step_kernel<NgSeq, BeamPen>), dim3(Na), dim3(64), 0, st, top_ids, top_lp, lp_sum, latest,
+                       gidx, tok_hist, par_hist, done, res_count, res_score, res_len, res_step, res_par, step, ctr,
+                       att, att_hist, pg, pg_hist, T, beam, K, stop_id, min_dec, max_dec, *ng, *pen);
+  else if (pen)
+    hipLaunchKernelGGL(beam_step_kernel<BeamPen>, dim3(Na), dim3(64), 0, st, top_ids, top_lp, lp_sum, latest, gidx,
+                       tok_hist, par_hist, done, res_count, res_score, res_len, res_step, res_par, step, ctr, att,
+                       att_hist, pg, pg_hist, T, beam, K, stop_id, min_dec, max_dec, *pen);
+  else if (ngram)
     hipLaunchKernelGGL(beam_step_kernel<NgSeq>, dim3(Na), dim3(64), 0, st, top_ids, top_lp, lp_sum, latest, gidx,
                        tok_hist, par_hist, done, res_count, res_score, res_len, res_step, res_par, step, ctr, att,
                        att_hist, pg, pg_hist, T, beam, K, stop_id, min_dec, max_dec, *ng);

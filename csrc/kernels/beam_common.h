@@ -3,6 +3,7 @@
 // rank by total log-prob, collect finished (STOP) hypotheses after min_dec steps, keep the
 // best ``beam`` live ones (reference beam_search.py:110-156).
 #pragma once
+#include <type_traits>
 #include "common.h"
 #include "launchers.h"
 
@@ -14,9 +15,17 @@
 // the hypothesis' last n - 1 tokens.  A blocked candidate's step log-prob becomes BLOCKED_LP: it
 // ranks behind every unblocked one and is taken only when nothing else is left.
 #define BLOCKED_LP (-1e20f)
-// the kernels' optional trailing NgSeq argument (a pack of zero or one)
+// the kernels' optional trailing arguments: a pack of zero or one NgSeq, then zero or one BeamPen
+template <typename T, typename... A>
+constexpr bool pack_has = (std::is_same_v<T, A> || ...);
 __device__ __forceinline__ NgSeq ng_of() { return NgSeq{}; }
 __device__ __forceinline__ NgSeq ng_of(const NgSeq& x) { return x; }
+__device__ __forceinline__ NgSeq ng_of(const BeamPen&) { return NgSeq{}; }
+__device__ __forceinline__ NgSeq ng_of(const NgSeq& x, const BeamPen&) { return x; }
+__device__ __forceinline__ BeamPen pen_of() { return BeamPen{}; }
+__device__ __forceinline__ BeamPen pen_of(const NgSeq&) { return BeamPen{}; }
+__device__ __forceinline__ BeamPen pen_of(const BeamPen& p) { return p; }
+__device__ __forceinline__ BeamPen pen_of(const NgSeq&, const BeamPen& p) { return p; }
 
 // The candidate-independent half of the test, once per article by the whole workgroup:
 // ban[i * P + e] = s_i[e] where the n - 1 tokens before e match hypothesis i's suffix, else -1
@@ -65,37 +74,60 @@ __device__ __forceinline__ void ngram_seq_advance(const int* __restrict__ seq_in
   }
 }
 
+// ------------------------------------------------------------------ length / coverage penalties
+// The rank key of a candidate with raw total tot of parent row ``row`` at step t (BeamPen,
+// launchers.h).  Contraction is off here: each product and the difference is rounded on its own,
+// so an fp32 mirror on the host reproduces every key bit for bit.
+__device__ __forceinline__ float pen_key(const BeamPen& pen, float tot, int t, int row) {
+#pragma clang fp contract(off)
+  float key = tot * pen.inv_len[t + 2];
+  if (pen.cpen) {
+    const float p = pen.beta * pen.cpen[row];
+    key = key - p;
+  }
+  return key;
+}
+
 // ------------------------------------------------------------------ beam bookkeeping
+// PEN (pen, ckey: one more [64] LDS array): rank by pen_key instead of the raw total, which is
+// still what lp_sum carries.
 // NG: also leaves each new hypothesis' parent slot and token in adv_par / adv_tok (LDS, [beam])
 // for ngram_seq_advance
-template <bool NG = false>
+template <bool NG = false, bool PEN = false>
 __device__ __forceinline__ void beam_step_body(
     const int* __restrict__ top_ids, const float* __restrict__ top_lp, float* __restrict__ lp_sum,
     int* __restrict__ latest, int* __restrict__ gidx, int* __restrict__ tok_hist, int* __restrict__ par_hist,
     int* __restrict__ done, int* __restrict__ res_count, float* __restrict__ res_score, int* __restrict__ res_len,
     int* __restrict__ res_step, int* __restrict__ res_par, float* cval, int* cid, int* srt, int a, int lane, int t,
     int base, int beam, int K, int stop_id, int min_dec, float tot, int tid_cand, int nres0, int Na,
-    int* adv_par = nullptr, int* adv_tok = nullptr) {
+    int* adv_par = nullptr, int* adv_tok = nullptr, const BeamPen& pen = BeamPen{}, float* ckey = nullptr) {
   // tot / tid_cand / nres0: this lane's candidate and the result count, loaded by the caller
   // in the same memory round trip as the step counter and the done flag
   const int norig = t == 0 ? 1 : beam;
   const int ncand = norig * K;
   if (lane >= ncand) tot = -INFINITY;
+  float key = tot;  // what the candidates are ranked by
+  if constexpr (PEN) {
+    // (lanes past ncand hold a row of the article -- rows >= 1 at t == 0 -- or lane / K >= beam)
+    key = lane < ncand ? pen_key(pen, tot, t, base + lane / K) : -INFINITY;
+  }
   // stable rank: descending total, ties keep candidate order (readlane: a uniform lane index,
   // no LDS permute per candidate)
   int rank = 0;
   for (int q = 0; q < ncand; ++q) {
-    const float v = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tot), q));
-    if (v > tot || (v == tot && q < lane)) ++rank;
+    const float v = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(key), q));
+    if (v > key || (v == key && q < lane)) ++rank;
   }
   if (lane < ncand) {  // rank-ordered candidate table: value, token, parent
     cval[rank] = tot;
+    if constexpr (PEN) ckey[rank] = key;
     cid[rank] = tid_cand;
     srt[rank] = lane / K;
   }
   __shared__ float nlp[BEAM_CAND_MAX];
   __shared__ int ntok[BEAM_CAND_MAX], npar[BEAM_CAND_MAX];
   __shared__ int nh_s, nres_s;
+  __shared__ float nkey[PEN ? BEAM_CAND_MAX : 1];
   __syncthreads();
   // The reference walks the ranked candidates in order: a STOP (from step min_dec on) becomes a
   // result, any other token a new hypothesis, until beam of either (beam_search.py:120-150).
@@ -115,13 +147,19 @@ __device__ __forceinline__ void beam_step_body(
     const int par = act ? srt[lane] : 0;
     if (reached && is_res) {
       const int slot = a * beam + nres0 + ns;
-      res_score[slot] = v / (float)(t + 2);
+      if constexpr (PEN) {
+        res_score[slot] = ckey[lane];
+        pen.res_lp[slot] = v;
+      } else {
+        res_score[slot] = v / (float)(t + 2);
+      }
       res_len[slot] = t + 2;
       res_step[slot] = t;
       res_par[slot] = par;
     }
     if (reached && is_hyp) {
       nlp[nn] = v;
+      if constexpr (PEN) nkey[nn] = ckey[lane];
       ntok[nn] = tok;
       npar[nn] = par;
     }
@@ -140,6 +178,7 @@ __device__ __forceinline__ void beam_step_body(
     const int kk = k < nh ? k : (nh > 0 ? nh - 1 : 0);
     const int par = nh > 0 ? npar[kk] : 0;
     lp_sum[base + k] = nh > 0 ? nlp[kk] : -INFINITY;
+    if constexpr (PEN) pen.key_sum[base + k] = nh > 0 ? nkey[kk] : -INFINITY;
     latest[base + k] = nh > 0 ? ntok[kk] : stop_id;
     gidx[base + k] = base + par;
     tok_hist[(size_t)t * Na * beam + base + k] = nh > 0 ? ntok[kk] : stop_id;
@@ -164,9 +203,11 @@ __device__ __forceinline__ void beam_step_body(
 // NG (n-gram blocking): the whole workgroup builds the article's ban table (ban: >= beam * ng.P
 // ints of LDS, 16-byte aligned) before the poll and advances the sequences after the bookkeeping
 // (adv: 2 * BEAM_CAND_MAX ints of LDS).
-template <bool NG = false>
+// PEN (length / coverage penalties): only the bookkeeping after the poll differs (beam_step_body).
+template <bool NG = false, bool PEN = false>
 __device__ __forceinline__ void beam_article_tail(const BeamTail& bt, int a, float* cval, int* cid, int* srt,
-                                                  const NgSeq& ng = NgSeq{}, int* ban = nullptr, int* adv = nullptr) {
+                                                  const NgSeq& ng = NgSeq{}, int* ban = nullptr, int* adv = nullptr,
+                                                  const BeamPen& pen = BeamPen{}, float* ckey = nullptr) {
   const int lane = threadIdx.x, beam = bt.beam, K = bt.K, base = a * beam;
   const size_t R = (size_t)bt.Na * beam;
   const int t = *bt.step - 1;
@@ -205,14 +246,16 @@ __device__ __forceinline__ void beam_article_tail(const BeamTail& bt, int a, flo
     __syncthreads();  // the ban table is complete
     if (lane < beam * K && ngram_banned(ban, lane / K, ng.P, t, tid_cand))
       tot = bt.lp_sum[base + lane / K] + BLOCKED_LP;
-    beam_step_body<true>(nullptr, nullptr, bt.lp_sum, bt.latest, bt.gidx, bt.tok_hist, bt.par_hist, bt.done,
-                         bt.res_count, bt.res_score, bt.res_len, bt.res_step, bt.res_par, cval, cid, srt, a, lane, t,
-                         base, beam, K, bt.stop_id, bt.min_dec, tot, tid_cand, nres0, bt.Na, adv, adv + BEAM_CAND_MAX);
+    beam_step_body<true, PEN>(nullptr, nullptr, bt.lp_sum, bt.latest, bt.gidx, bt.tok_hist, bt.par_hist, bt.done,
+                              bt.res_count, bt.res_score, bt.res_len, bt.res_step, bt.res_par, cval, cid, srt, a, lane,
+                              t, base, beam, K, bt.stop_id, bt.min_dec, tot, tid_cand, nres0, bt.Na, adv,
+                              adv + BEAM_CAND_MAX, pen, ckey);
     __syncthreads();  // the new hypotheses' parents / tokens written by lanes < beam
     ngram_seq_advance(ng.seq[t & 1], ng.seq[(t + 1) & 1], adv, adv + BEAM_CAND_MAX, base, beam, ng.P, t, (int)R);
   } else {
-    beam_step_body(nullptr, nullptr, bt.lp_sum, bt.latest, bt.gidx, bt.tok_hist, bt.par_hist, bt.done, bt.res_count,
-                   bt.res_score, bt.res_len, bt.res_step, bt.res_par, cval, cid, srt, a, lane, t, base, beam, K,
-                   bt.stop_id, bt.min_dec, tot, tid_cand, nres0, bt.Na);
+    beam_step_body<false, PEN>(nullptr, nullptr, bt.lp_sum, bt.latest, bt.gidx, bt.tok_hist, bt.par_hist, bt.done,
+                               bt.res_count, bt.res_score, bt.res_len, bt.res_step, bt.res_par, cval, cid, srt, a, lane,
+                               t, base, beam, K, bt.stop_id, bt.min_dec, tot, tid_cand, nres0, bt.Na, nullptr, nullptr,
+                               pen, ckey);
   }
 }

@@ -101,12 +101,28 @@ struct NgSeq {
   int P;  // row pitch: >= max_dec + 1, a multiple of 4
   int n;
 };
+// Length / coverage penalties of the beam bookkeeping (beam_common.h): candidates are ranked by
+//   key = tot * inv_len[t + 2] - beta * cpen[row of the parent]
+// (two fp32 products and one difference, each rounded to nearest, no FMA) instead of the raw sum
+// tot; finished hypotheses keep key in res_score and tot in res_lp, new hypotheses key in
+// key_sum and tot in lp_sum.  No BeamPen: off, the kernels without it run.
+struct BeamPen {
+  const float* inv_len;  // [max_dec + 2]: 1 / L(n) per hypothesis length n (tokens, [START] included)
+  const float* cpen;     // [R] this step's coverage penalty per parent row (launch_cov_penalty), or null
+  float beta;
+  float* key_sum;        // [R]
+  float* res_lp;         // [R]
+};
+// cpen[r] = sum_{i < lens[r / beam]} max(cov[r][i] + att[r][i] - 1, 0), one wave per row
+// (a0, optional [R / beam][T]: cov[r] - a0[r / beam] in place of cov[r])
+void launch_cov_penalty(const float* cov, const float* att, const int* lens, float* cpen, int R, int T, int beam,
+                        hipStream_t st, const float* a0 = nullptr);
 int topk_split(int V);
 void launch_beam_step(const int* top_ids, const float* top_lp, float* lp_sum, int* latest, int* gidx, int* tok_hist,
                       int* par_hist, int* done, int* res_count, float* res_score, int* res_len, int* res_step,
                       int* res_par, int* step, unsigned* ctr, const float* att, float* att_hist, const float* pg,
                       float* pg_hist, int T, int Na, int beam, int K, int stop_id, int min_dec, int max_dec,
-                      hipStream_t st, const NgSeq* ng = nullptr);
+                      hipStream_t st, const NgSeq* ng = nullptr, const BeamPen* pen = nullptr);
 void launch_beam_gather(const int* gidx, const int* latest, const float* c_src, const bf16* h_src,
                         const float* ctx_src, const float* a_src, const float* cov_src, const float* XGtab,
                         const float* Xtab, float* c_out, bf16* h_out, float* ctx_out, bf16* ctxb_out, float* cov_out,
@@ -161,7 +177,7 @@ struct PgIn {
 void launch_vocab_topk(const bf16* X, const bf16* WT, const float* bias, const float* pgen, const float* attn,
                        const int* ext, const int* lens, int* out_ids, float* out_lp, float* logits, float* part_ms,
                        int R, int V, int H, int T, int K, int beam, PgIn pgi, hipStream_t st,
-                       const BeamTail* bt = nullptr, const NgSeq* ng = nullptr);
+                       const BeamTail* bt = nullptr, const NgSeq* ng = nullptr, const BeamPen* pen = nullptr);
 int vocab_train_tiles(int V, int H);
 void launch_vocab_train_fwd(const bf16* X, int ldx, const bf16* WT, const float* bias, const int* target, float* part,
                             float* zg, float* lse, float* pv, int N, int V, int H, const int* vblk, const int* vblk_n,

@@ -566,15 +566,17 @@ __device__ unsigned long long* vs_stamps = nullptr;
     }                                                                                  \
   } while (0)
 // n-gram blocking in the beam tail (beam_common.h): instantiated with one trailing NgSeq argument
-// (without it the kernel and its arguments are exactly the plain one); its ban table reuses ci
+// (without it the kernel and its arguments are exactly the plain one); its ban table reuses ci.
+// Length / coverage penalties in the beam tail: one trailing BeamPen argument, in the same way.
 template <bool STAMP = false, typename... NGA>
 __global__ __launch_bounds__(VS_THREADS) void vocab_select_kernel(
     const float* __restrict__ logits, const float* __restrict__ part_ms, const float* __restrict__ pgen,
     const float* __restrict__ attn, const int* __restrict__ ext, const int* __restrict__ lens,
     int* __restrict__ out_ids, float* __restrict__ out_lp, int V, int T, int K, int beam, int nt, int tcols, PgIn pgi,
     BeamTail bt, int span, NGA... nga) {  // span: partials of vocab_logits_span_kernel (nt = NW waves, [G][R][8], vp_lo columns)
-  constexpr bool NG = sizeof...(NGA) == 1;
+  constexpr bool NG = pack_has<NgSeq, NGA...>, PEN = pack_has<BeamPen, NGA...>;
   __shared__ float bt_cval[64];
+  __shared__ float bt_ckey[PEN ? 64 : 1];
   __shared__ int bt_cid[64], bt_srt[64];
   __shared__ int bt_last;
   __shared__ int hkey[VM_HASH];
@@ -817,7 +819,11 @@ __global__ __launch_bounds__(VS_THREADS) void vocab_select_kernel(
     if (bt_last) {
       if (tid == 0) __hip_atomic_store(&bt.art_ctr[art], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if constexpr (NG)  // (ci, cv: every read of them ended before the barriers above)
-        beam_article_tail<true>(bt, art, bt_cval, bt_cid, bt_srt, ng_of(nga...), ci, reinterpret_cast<int*>(cv));
+        beam_article_tail<true, PEN>(bt, art, bt_cval, bt_cid, bt_srt, ng_of(nga...), ci, reinterpret_cast<int*>(cv),
+                                     pen_of(nga...), bt_ckey);
+      else if constexpr (PEN)
+        beam_article_tail<false, true>(bt, art, bt_cval, bt_cid, bt_srt, NgSeq{}, nullptr, nullptr, pen_of(nga...),
+                                       bt_ckey);
       else
         beam_article_tail(bt, art, bt_cval, bt_cid, bt_srt);
     }
@@ -862,11 +868,12 @@ int vocab_topk_tiles(int V, int H) { return vp_use(H) ? vp_groups(V) : (V + vt_c
 void launch_vocab_topk(const bf16* X, const bf16* WT, const float* bias, const float* pgen, const float* attn,
                        const int* ext, const int* lens, int* out_ids, float* out_lp, float* logits, float* part_ms,
                        int R, int V, int H, int T, int K, int beam, PgIn pgi, hipStream_t st, const BeamTail* bt,
-                       const NgSeq* ng) {
+                       const NgSeq* ng, const BeamPen* pen) {
   const int nt = vocab_topk_tiles(V, H);
   const BeamTail none{};
   const bool ngram = bt && ng && ng->n > 1;  // (the stamp build of the select kernel is without it)
   const NgSeq ngv = ngram ? *ng : NgSeq{};
+  const bool pens = bt && pen;  // length / coverage penalties in the beam tail
   const bool span = vp_use(H);
   if (span) {
     const size_t lds = (size_t)vp_xrows(H, R) * (2 * H + 8 * VP_WAVES);
@@ -880,7 +887,14 @@ void launch_vocab_topk(const bf16* X, const bf16* WT, const float* bias, const f
     else if (H == 256) VPL(256);
     else VPL(512);
 #undef VPL
-    if (ngram)
+    if (pens && ngram)
+      hipLaunchKernelGGL((vocab_select_kernel<false, NgSeq, BeamPen>), dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms,
+                         pgen, attn, ext, lens, out_ids, out_lp, V, T, K, beam, nt, 16 * VP_NI * VP_WAVES, pgi, *bt, 1,
+                         ngv, *pen);
+    else if (pens)
+      hipLaunchKernelGGL((vocab_select_kernel<false, BeamPen>), dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms, pgen,
+                         attn, ext, lens, out_ids, out_lp, V, T, K, beam, nt, 16 * VP_NI * VP_WAVES, pgi, *bt, 1, *pen);
+    else if (ngram)
       hipLaunchKernelGGL((vocab_select_kernel<false, NgSeq>), dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms, pgen, attn,
                          ext, lens, out_ids, out_lp, V, T, K, beam, nt, 16 * VP_NI * VP_WAVES, pgi, *bt, 1, ngv);
     else if (vs_stamp_host)
@@ -906,7 +920,13 @@ void launch_vocab_topk(const bf16* X, const bf16* WT, const float* bias, const f
     hipLaunchKernelGGL((vocab_logits_kernel<2, 1, 512, true>), dim3(8 * RB * ((nt + 7) / 8)), dim3(256), 0, st, X, WT,
                        bias, logits, part_ms, R, V, H);
   }
-  if (ngram)
+  if (pens && ngram)
+    hipLaunchKernelGGL((vocab_select_kernel<false, NgSeq, BeamPen>), dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms,
+                       pgen, attn, ext, lens, out_ids, out_lp, V, T, K, beam, nt, tcols, pgi, *bt, 0, ngv, *pen);
+  else if (pens)
+    hipLaunchKernelGGL((vocab_select_kernel<false, BeamPen>), dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms, pgen,
+                       attn, ext, lens, out_ids, out_lp, V, T, K, beam, nt, tcols, pgi, *bt, 0, *pen);
+  else if (ngram)
     hipLaunchKernelGGL((vocab_select_kernel<false, NgSeq>), dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms, pgen, attn,
                        ext, lens, out_ids, out_lp, V, T, K, beam, nt, tcols, pgi, *bt, 0, ngv);
   else

@@ -70,6 +70,11 @@ class HParams:
     decode_batch: int = 64         # articles decoded together (beam-as-batch x articles)
     block_ngram_repeat: int = 0    # beam search: a candidate that would repeat an n-gram of its hypothesis
                                    # gets log-prob -1e20 (3 = trigram blocking; 0 / 1 = off)
+    length_penalty: str = "avg"    # beam search ranks by sum(log-probs) / L(len): avg L = len (the reference),
+                                   # wu L = ((5 + len) / 6) ** length_alpha (GNMT), none L = 1
+    length_alpha: float = 0.9      # used by length_penalty = wu only
+    coverage_penalty_beta: float = 0.0  # beam search: minus beta * sum_i max(coverage_i - 1, 0), the summary
+                                        # penalty of Gehrmann et al. 2018 (needs coverage = 1; 0 = off)
     stream_max_wait_ms: float = 0.0   # streaming decode: queued requests always share a batch; after
                                       # the first, wait at most this long for more (0 = no waiting)
     save_model_secs: int = 60      # Supervisor(save_model_secs=60), run_summarization.py:199
@@ -167,6 +172,20 @@ def decode_hps(hps: HParams) -> HParams:
     return hps.replace(batch_size=hps.beam_size)
 
 
+LENGTH_PENALTIES = ("avg", "wu", "none")
+
+
+def check_penalties(hps) -> None:
+    """The beam-search length / coverage penalty options (host and device searches refuse the same)."""
+    if hps.length_penalty not in LENGTH_PENALTIES:
+        raise ValueError(f"length_penalty must be one of {'/'.join(LENGTH_PENALTIES)}")
+    if not hps.length_alpha >= 0 or not hps.coverage_penalty_beta >= 0:
+        raise ValueError("length_alpha and coverage_penalty_beta must be >= 0")
+    if hps.coverage_penalty_beta > 0 and not hps.coverage:
+        raise ValueError("coverage_penalty_beta > 0 needs coverage=True: the coverage vector is only kept "
+                         "for coverage models")
+
+
 def check_hps(hps: HParams) -> None:
     if hps.mode not in ("train", "eval", "decode"):
         raise ValueError("The 'mode' flag must be one of train/eval/decode")
@@ -177,6 +196,7 @@ def check_hps(hps: HParams) -> None:
                          "convert_to_coverage_model=True and coverage=True")  # :188
     if hps.block_ngram_repeat < 0:
         raise ValueError("block_ngram_repeat must be >= 0 (0 or 1 = off)")
+    check_penalties(hps)
 
 
 @dataclass

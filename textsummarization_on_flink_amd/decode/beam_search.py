@@ -16,6 +16,12 @@ Not in the reference: ``hps.block_ngram_repeat = n`` (n >= 2) blocks repeated n-
 keeps its place among the hypothesis' top 2*beam candidates, but its step log-prob becomes
 ``BLOCKED_LP``, so it ranks behind every unblocked candidate (OpenNMT-py's block_ngram_repeat).
 
+Also not in the reference: a length penalty and the summary coverage penalty of Gehrmann et al.
+2018 (``hps.length_penalty``, ``hps.length_alpha``, ``hps.coverage_penalty_beta``; ``hyp_score``).
+With them the search ranks -- at every step, for the result score and for the final pick -- by
+``score(h) = log_prob / L(len(tokens)) - beta * cp(h)`` instead of the average log-prob; the
+defaults (``avg``, beta 0) are the reference's rule and take the reference's path.
+
 The step model is pluggable (``StepModel``): the PyTorch oracle on CPU, or the gfx950
 decode step on GPU.  The batched device-resident version (many articles per launch,
 hipGraph-captured) lives in ``decode.device_beam``.
@@ -28,6 +34,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
+from ..config import check_penalties
 from ..data.vocab import START_DECODING, STOP_DECODING, UNKNOWN_TOKEN
 
 
@@ -39,6 +46,7 @@ class Hypothesis:
     attn_dists: List[np.ndarray] = field(default_factory=list)
     p_gens: List[Optional[float]] = field(default_factory=list)
     coverage: Optional[np.ndarray] = None
+    score: Optional[float] = None  # the ranking score (``hyp_score``) of a returned hypothesis
 
     def extend(self, token, log_prob, state, attn_dist, p_gen, coverage) -> "Hypothesis":
         return Hypothesis(self.tokens + [token], self.log_probs + [log_prob], state, self.attn_dists + [attn_dist],
@@ -74,6 +82,57 @@ def ngram_blocked(tokens, w: int, n: int) -> bool:
 
 def sort_hyps(hyps: List[Hypothesis]) -> List[Hypothesis]:
     return sorted(hyps, key=lambda h: h.avg_log_prob, reverse=True)
+
+
+def penalties_on(hps) -> bool:
+    """False for the reference's rule (average log-prob, no coverage penalty)."""
+    return getattr(hps, "length_penalty", "avg") != "avg" or float(getattr(hps, "coverage_penalty_beta", 0.0)) > 0
+
+
+def length_norm(n: int, kind: str = "avg", alpha: float = 0.9) -> float:
+    """L(n) for a hypothesis of n tokens ([START] included): ``avg`` n, ``wu`` ((5 + n) / 6) ** alpha
+    (GNMT), ``none`` 1."""
+    if kind == "avg":
+        return float(n)
+    if kind == "wu":
+        return ((5.0 + n) / 6.0) ** float(alpha)
+    if kind == "none":
+        return 1.0
+    raise ValueError(f"unknown length_penalty {kind!r}")
+
+
+def inv_len_table(hps, nmax: int) -> np.ndarray:
+    """1 / L(n) for n = 0 .. nmax, computed in fp64 and rounded once to fp32 (entry 0 unused): the
+    table the device bookkeeping multiplies the log-prob sums with."""
+    n = np.arange(nmax + 1)
+    n[0] = 1
+    return np.array([1.0 / length_norm(int(x), hps.length_penalty, hps.length_alpha) for x in n], np.float32)
+
+
+def coverage_penalty(cov_total, enc_len: int) -> float:
+    """sum over article positions i < enc_len of max(c_i - 1, 0), c = the sum of a hypothesis'
+    attention distributions (OpenNMT-py's ``summary`` penalty, sum(max(cov, 1)) - src_len)."""
+    c = np.asarray(cov_total, np.float64)[:int(enc_len)]
+    return float(np.maximum(c - 1.0, 0.0).sum())
+
+
+def hyp_score(h: Hypothesis, hps, enc_len: int) -> float:
+    """The ranking score: log_prob / L(len(tokens)) - beta * cp, cp over the sum of the attention
+    distributions of every step taken; plain Python floats.  (Not ``h.coverage`` plus the last
+    attention: the coverage of the decode graph also holds the initial-state attention of step
+    0, which is no step of the hypothesis.)"""
+    s = h.log_prob / length_norm(len(h.tokens), getattr(hps, "length_penalty", "avg"),
+                                 getattr(hps, "length_alpha", 0.9))
+    beta = float(getattr(hps, "coverage_penalty_beta", 0.0))
+    if beta > 0 and h.attn_dists:
+        if not hps.coverage or h.coverage is None:
+            raise ValueError("coverage_penalty_beta > 0 needs coverage=True")
+        s -= beta * coverage_penalty(np.sum(np.asarray(h.attn_dists, np.float64), 0), enc_len)
+    return s
+
+
+def sort_by_score(hyps: List[Hypothesis]) -> List[Hypothesis]:
+    return sorted(hyps, key=lambda h: h.score, reverse=True)
 
 
 class OracleStepModel:
@@ -120,6 +179,13 @@ def run_beam_search(model, vocab, batch, hps) -> Hypothesis:
     results: List[Hypothesis] = []
     steps = 0
     ngram = int(getattr(hps, "block_ngram_repeat", 0))
+    pen = penalties_on(hps)
+    rank = sort_by_score if pen else sort_hyps
+    if pen:
+        check_penalties(hps)
+        enc_len = int(batch.enc_lens[0])
+        for h in hyps:
+            h.score = hyp_score(h, hps, enc_len)
     while steps < hps.max_dec_steps and len(results) < hps.beam_size:
         latest = [h.latest_token if h.latest_token < V else unk for h in hyps]
         ids, lps, new_states, attn, pgens, covs = model.decode_onestep(
@@ -133,8 +199,10 @@ def run_beam_search(model, vocab, batch, hps) -> Hypothesis:
                 if ngram > 1 and ngram_blocked(hyps[i].tokens, tok, ngram):
                     lp = BLOCKED_LP
                 all_hyps.append(hyps[i].extend(tok, lp, new_states[i], attn[i], pgens[i], covs[i]))
+                if pen:
+                    all_hyps[-1].score = hyp_score(all_hyps[-1], hps, enc_len)
         hyps = []
-        for h in sort_hyps(all_hyps):
+        for h in rank(all_hyps):
             if h.latest_token == stop:
                 if steps >= hps.min_dec_steps:
                     results.append(h)
@@ -145,4 +213,7 @@ def run_beam_search(model, vocab, batch, hps) -> Hypothesis:
         steps += 1
     if not results:
         results = hyps
-    return sort_hyps(results)[0]
+    best = rank(results)[0]
+    if best.score is None:  # the reference's rule, or no step taken
+        best.score = best.avg_log_prob
+    return best

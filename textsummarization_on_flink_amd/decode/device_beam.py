@@ -34,13 +34,16 @@ from ..models.pointer_generator import (ATT_B, CELL_B, CELL_K, EMB, LIN_B, LIN_M
                                         HipPointerGenerator, mmf)
 from ..models.engine_config import EngineConfig
 from ..utils.graphs import capture_guard
-from .beam_search import Hypothesis
+from ..config import check_penalties
+from .beam_search import Hypothesis, inv_len_table, penalties_on
 
 BF = torch.bfloat16
 F32 = torch.float32
 
 
 class DeviceBeamDecoder:
+    pen = None  # length / coverage penalties off unless __init__ finds them in hps
+
     def __init__(self, hps, vocab, params, n_articles: int, T: int, use_graph: bool = True, chunk: int = 10,
                  keep_attn: bool = True):
         self.hps, self.vocab, self.p = hps, vocab, params
@@ -60,6 +63,10 @@ class DeviceBeamDecoder:
         if n < 0:
             raise ValueError("block_ngram_repeat must be >= 0")
         self.ngram = n if n > 1 else 0
+        # length / coverage penalties (beam_search.hyp_score) in the bookkeeping of both step variants:
+        # None = the reference's rule, the kernels and buffers without them
+        check_penalties(hps)
+        self.pen = {"beta": float(hps.coverage_penalty_beta)} if penalties_on(hps) else None
         # decode steps per captured graph: a whole early-exit chunk when it is even (one graph
         # launch per chunk instead of one per step pair), else 2
         self.gsteps = chunk if chunk % 2 == 0 else 2
@@ -152,6 +159,15 @@ class DeviceBeamDecoder:
                 raise ValueError(f"block_ngram_repeat: beam_size * (max_dec_steps + 1) = {self.beam * (D + 1)} "
                                  "exceeds the 4096 tokens per article the beam kernels hold")
             self.seq = [z(R, P, dt=torch.int32) for _ in range(2)]
+        # penalties: the rank key of every live hypothesis and the raw sum of every result (res_score
+        # then holds the key), 1 / L(n) per length, this step's coverage penalty per row (beta > 0)
+        if self.pen is not None:
+            b["key_sum"], b["res_lp"] = z(R), z(R)
+            b["inv_len"] = torch.from_numpy(inv_len_table(self.hps, D + 1)).to(self.dev)
+            if self.pen["beta"] > 0:
+                # (att0: the step-0 initial-state attention per article, which the coverage holds
+                # but which is no step of a hypothesis)
+                b["cpen"], b["att0"] = z(R), z(Na, T)
         self.b = b
 
     def refresh_weights(self):
@@ -254,6 +270,12 @@ class DeviceBeamDecoder:
                   "art_ctr", "gran"):
             b[n].zero_()
         b["res_score"].fill_(-float("inf"))
+        if self.pen is not None:
+            b["key_sum"].zero_()
+            b["res_lp"].fill_(-float("inf"))
+            if "cpen" in b:
+                b["cpen"].zero_()
+                b["att0"].copy_(X["ATT"][::self.beam])
         if self.seq is not None:
             self.seq[0].zero_()
             self.seq[0][:, 0] = self.vocab.word2id(START_DECODING)
@@ -315,10 +337,25 @@ class DeviceBeamDecoder:
                 None, Y["ATT"] if hist else None, b["ATT_hist"] if hist else None,
                 pg if (hist and pg is not None) else None, b["PG_hist"] if (hist and pg is not None) else None,
                 T, self.Na, self.beam, K, self.vocab.word2id(STOP_DECODING), hps.min_dec_steps, self.maxD)
-        if self.ngram:
+        if self.pen is not None:
+            self._cov_penalty(Y)
+            k.beam_step_pen(*args, *self._pen_args())
+        elif self.ngram:
             k.beam_step_ng(*args, self.seq[0], self.seq[1], self.ngram)
         else:
             k.beam_step(*args)
+
+    def _cov_penalty(self, Y):
+        """This step's coverage penalty per row from the coverage before the step and its attention
+        (after the attention, before the bookkeeping; only with beta > 0)."""
+        if "cpen" in self.b:
+            self.k.cov_penalty(Y["COV"], Y["ATT"], self.b["lens"], self.b["cpen"], self.R, self.T, self.beam,
+                               self.b["att0"])
+
+    def _pen_args(self):
+        b = self.b
+        seq = self.seq if self.ngram else (None, None)
+        return (seq[0], seq[1], self.ngram, b["inv_len"], b.get("cpen"), self.pen["beta"], b["key_sum"], b["res_lp"])
 
     def _step_fused(self, parity: int):
         """One decode step in 6 launches (reference model.py:367-443 decode_onestep + the beam
@@ -340,6 +377,8 @@ class DeviceBeamDecoder:
         k.attn_fwd_row_beam(b["F"], b["E"], b["s"], eng.f32["v"], eng.f32["wc"], X["COV"] if cov else None,
                             X["ATT"] if cov else None, Y["COV"] if cov else None, b["gidx"], b["lens_att"],
                             Y["ATT"], Y["CTX"], Y["CTXb"], R, T, A, self.rep)
+        if self.pen is not None:
+            self._cov_penalty(Y)
         k.linear2(Y["H"], H, Y["CTXb"], A, eng.pk["OUTmT"], p[OUT_B], None, None, b["outb"], R, H)
         ptr, hist = hps.pointer_gen, self.keep_attn
         args = (b["outb"], self.owT, p[OV], Y["CTX"] if ptr else None, Y["C"] if ptr else None,
@@ -351,7 +390,9 @@ class DeviceBeamDecoder:
                 b["gran"], b["tail_err"],
                 b["ATT_hist"] if hist else None, b["PG_hist"] if (hist and ptr) else None, R, V, H, T, K,
                 self.beam, A, E, self.vocab.word2id(STOP_DECODING), hps.min_dec_steps, self.maxD)
-        if self.ngram:
+        if self.pen is not None:
+            k.vocab_topk_beam_pen(*args, *self._pen_args())
+        elif self.ngram:
             k.vocab_topk_beam_ng(*args, self.seq[0], self.seq[1], self.ngram)
         else:
             k.vocab_topk_beam(*args)
@@ -460,6 +501,7 @@ class DeviceBeamDecoder:
 
     def _result_names(self):
         names = ["res_count", "res_score", "res_step", "res_par", "lp_sum", "tok_hist", "par_hist", "step"]
+        names += ["key_sum", "res_lp"] if self.pen is not None else []
         return names + (["ATT_hist", "PG_hist"] if self.keep_attn else [])
 
     def results(self, n_valid: int = None) -> List[Hypothesis]:
@@ -621,9 +663,14 @@ class DeviceBeamDecoder:
         rs = b["res_score"][:na * beam].reshape(na, beam).astype(np.float64)
         rs = np.where(np.arange(beam)[None, :] < nres[:, None], rs, -np.inf)
         q_fin = rs.argmax(1) if na else np.zeros(0, np.int64)
-        live = b["lp_sum"][:na * beam].reshape(na, beam).astype(np.float64) / (nsteps + 1)
+        lps = b["lp_sum"][:na * beam].reshape(na, beam).astype(np.float64)
+        pen = self.pen is not None
+        # (penalties: res_score and key_sum hold the rank keys, res_lp and lp_sum the raw sums)
+        live = b["key_sum"][:na * beam].reshape(na, beam).astype(np.float64) if pen else lps / (nsteps + 1)
         q_live = live.argmax(1) if na else np.zeros(0, np.int64)
         score = np.where(fin, rs[ar, q_fin], live[ar, q_live])
+        if pen:
+            lp_tot = np.where(fin, b["res_lp"][base + q_fin].astype(np.float64), lps[ar, q_live])
         t_fin = b["res_step"][base + q_fin].astype(np.int64)
         tl0 = np.where(fin, t_fin - 1, nsteps - 1)
         slot = np.where(fin, b["res_par"][base + q_fin], q_live).astype(np.int64)
@@ -651,14 +698,16 @@ class DeviceBeamDecoder:
                     atts.append(b["ATT_hist"][t, base[a] + par].copy())
                     pgs.append(float(b["PG_hist"][t, base[a] + par]) if self.hps.pointer_gen else None)
             sc = float(score[a])
-            out.append(Hypothesis(tokens, [sc * len(tokens)] + [0.0] * (len(tokens) - 1), None, atts, pgs, None))
+            lp = float(lp_tot[a]) if pen else sc * len(tokens)
+            out.append(Hypothesis(tokens, [lp] + [0.0] * (len(tokens) - 1), None, atts, pgs, None, sc))
         return out
 
     def _results_walk(self, n_valid: int = None) -> List[Hypothesis]:
         """Per-candidate Python walk (the original form of ``results``; kept as the test oracle)."""
         b = {k: v.cpu().numpy() for k, v in self.b.items() if k in (
             "res_count", "res_score", "res_len", "res_step", "res_par", "lp_sum", "tok_hist", "par_hist", "step",
-            "ATT_hist", "PG_hist", "done")}
+            "ATT_hist", "PG_hist", "done", "key_sum", "res_lp")}
+        pen = self.pen is not None
         beam, start, stop = self.beam, self.vocab.word2id(START_DECODING), self.vocab.word2id(STOP_DECODING)
         nsteps = int(min(b["step"][0], self.maxD))
         out = []
@@ -686,15 +735,18 @@ class DeviceBeamDecoder:
                     if self.keep_attn:
                         atts = atts + [b["ATT_hist"][t, base + par]]
                         pgs = pgs + [float(b["PG_hist"][t, base + par]) if self.hps.pointer_gen else None]
-                    cands.append((float(b["res_score"][base + q]), [start] + toks + [stop], atts, pgs))
+                    cands.append((float(b["res_score"][base + q]), [start] + toks + [stop], atts, pgs,
+                                  float(b["res_lp"][base + q]) if pen else None))
             else:
                 tl = nsteps - 1
                 for slot in range(beam):
                     toks, atts, pgs = path(tl, slot)
-                    cands.append((float(b["lp_sum"][base + slot]) / (tl + 2), [start] + toks, atts, pgs))
+                    lp = float(b["lp_sum"][base + slot])
+                    cands.append((float(b["key_sum"][base + slot]) if pen else lp / (tl + 2), [start] + toks, atts,
+                                  pgs, lp))
             best = sorted(cands, key=lambda c: c[0], reverse=True)[0]  # stable, like sort_hyps
-            h = Hypothesis(best[1], [best[0] * len(best[1])] + [0.0] * (len(best[1]) - 1), None,
-                           list(best[2]), list(best[3]), None)
+            h = Hypothesis(best[1], [best[4] if pen else best[0] * len(best[1])] + [0.0] * (len(best[1]) - 1), None,
+                           list(best[2]), list(best[3]), None, best[0])
             out.append(h)
         return out
 
