@@ -884,13 +884,16 @@ void clip_adagrad(const Tensor& w, const Tensor& acc, const Tensor& g, const Ten
 int64_t opt_parts() { return opt_nparts(); }
 
 // ---------------------------------------------------------------- beam search
-void final_topk(const Tensor& logits, const Tensor& bias, const OT& pgen, const OT& attn, const Tensor& ext,
-                const Tensor& lens, const Tensor& out_ids, const Tensor& out_lp, const Tensor& part_ms,
-                const Tensor& part_v, const Tensor& part_i, int64_t R, int64_t V, int64_t T, int64_t K, int64_t beam) {
+// K <= 16 runs the kernels with the 16-entry candidate list, 17..32 (or wide, any K <= 32) the
+// ones with the 32-entry list; part_v / part_i hold K entries per vocabulary split either way.
+static void final_topk_run(const Tensor& logits, const Tensor& bias, const OT& pgen, const OT& attn, const Tensor& ext,
+                           const Tensor& lens, const Tensor& out_ids, const Tensor& out_lp, const Tensor& part_ms,
+                           const Tensor& part_v, const Tensor& part_i, int64_t R, int64_t V, int64_t T, int64_t K,
+                           int64_t beam, bool wide) {
   chk(logits, F32, "logits"); chk(bias, F32, "bias"); chk(ext, I32, "ext"); chk(lens, I32, "lens");
   chk(out_ids, I32, "out_ids"); chk(out_lp, F32, "out_lp"); chk(part_ms, F32, "part_ms"); chk(part_v, F32, "part_v");
   chk(part_i, I32, "part_i");
-  TORCH_CHECK(K >= 1 && K <= 16 && beam >= 1 && R % beam == 0 && T <= 2048, "bad topk args");
+  TORCH_CHECK(K >= 1 && K <= 32 && beam >= 1 && R % beam == 0 && T <= 2048, "bad topk args (K <= 32)");
   numel_eq(logits, R * V, "logits"); numel_eq(bias, V, "bias"); numel_eq(ext, (R / beam) * T, "ext");
   numel_eq(lens, R / beam, "lens"); numel_eq(out_ids, R * K, "out_ids"); numel_eq(out_lp, R * K, "out_lp");
   TORCH_CHECK(topk_split(V) <= 64, "vocab too large for final_topk");
@@ -900,7 +903,19 @@ void final_topk(const Tensor& logits, const Tensor& bias, const OT& pgen, const 
   TORCH_CHECK(!PO<float>(pgen) || PO<float>(attn), "pointer mode needs attn");
   launch_final_topk(P<float>(logits), P<float>(bias), PO<float>(pgen), PO<float>(attn), P<int>(ext), P<int>(lens),
                     P<int>(out_ids), P<float>(out_lp), P<float>(part_ms), P<float>(part_v), P<int>(part_i), R, V, T, K,
-                    beam, stream());
+                    beam, stream(), wide);
+}
+void final_topk(const Tensor& logits, const Tensor& bias, const OT& pgen, const OT& attn, const Tensor& ext,
+                const Tensor& lens, const Tensor& out_ids, const Tensor& out_lp, const Tensor& part_ms,
+                const Tensor& part_v, const Tensor& part_i, int64_t R, int64_t V, int64_t T, int64_t K, int64_t beam) {
+  final_topk_run(logits, bias, pgen, attn, ext, lens, out_ids, out_lp, part_ms, part_v, part_i, R, V, T, K, beam, false);
+}
+// final_topk through the 32-entry-list kernels whatever K is (the wide-beam decode path)
+void final_topk_wide(const Tensor& logits, const Tensor& bias, const OT& pgen, const OT& attn, const Tensor& ext,
+                     const Tensor& lens, const Tensor& out_ids, const Tensor& out_lp, const Tensor& part_ms,
+                     const Tensor& part_v, const Tensor& part_i, int64_t R, int64_t V, int64_t T, int64_t K,
+                     int64_t beam) {
+  final_topk_run(logits, bias, pgen, attn, ext, lens, out_ids, out_lp, part_ms, part_v, part_i, R, V, T, K, beam, true);
 }
 int64_t topk_parts(int64_t V) { return topk_split(V); }
 
@@ -1195,13 +1210,19 @@ static void beam_step_run(const Tensor& top_ids, const Tensor& top_lp, const Ten
                const Tensor& res_count, const Tensor& res_score, const Tensor& res_len, const Tensor& res_step,
                const Tensor& res_par, const Tensor& step, const OT& ctr, const OT& att, const OT& att_hist,
                const OT& pg, const OT& pg_hist, int64_t T, int64_t Na, int64_t beam, int64_t K, int64_t stop_id,
-               int64_t min_dec, int64_t max_dec, const OT& seq0, const OT& seq1, int64_t ngram, const BeamPen* pen) {
+               int64_t min_dec, int64_t max_dec, const OT& seq0, const OT& seq1, int64_t ngram, const BeamPen* pen,
+               bool wide = false) {
   chk(top_ids, I32, "top_ids"); chk(top_lp, F32, "top_lp"); chk(lp_sum, F32, "lp_sum"); chk(latest, I32, "latest");
   chk(gidx, I32, "gidx"); chk(tok_hist, I32, "tok_hist"); chk(par_hist, I32, "par_hist"); chk(done, I32, "done");
   chk(res_count, I32, "res_count"); chk(res_score, F32, "res_score"); chk(res_len, I32, "res_len");
   chk(res_step, I32, "res_step"); chk(res_par, I32, "res_par"); chk(step, I32, "step"); chko(ctr, I32, 1, "ctr");
   const int64_t R = Na * beam;
-  TORCH_CHECK(beam >= 1 && beam <= 16 && K >= 1 && K <= 16 && beam * K <= 64, "bad beam args");
+  if (wide) {  // one workgroup per article: up to 16 * 32 candidates, no stand-alone step counter
+    TORCH_CHECK(beam >= 1 && beam <= 16 && K >= 1 && K <= 32 && beam * K <= 512 && !PO<int>(ctr),
+                "bad wide beam args (beam <= 16, K <= 32, no ctr)");
+  } else {
+    TORCH_CHECK(beam >= 1 && beam <= 16 && K >= 1 && K <= 16 && beam * K <= 64, "bad beam args");
+  }
   numel_eq(top_ids, R * K, "top_ids"); numel_eq(top_lp, R * K, "top_lp"); numel_eq(lp_sum, R, "lp_sum");
   numel_eq(latest, R, "latest"); numel_eq(gidx, R, "gidx"); numel_eq(tok_hist, max_dec * R, "tok_hist");
   numel_eq(par_hist, max_dec * R, "par_hist"); numel_eq(done, Na, "done"); numel_eq(res_count, Na, "res_count");
@@ -1212,6 +1233,14 @@ static void beam_step_run(const Tensor& top_ids, const Tensor& top_lp, const Ten
   chko(att, F32, R * T, "att"); chko(att_hist, F32, max_dec * R * T, "att_hist");
   chko(pg, F32, R, "pg"); chko(pg_hist, F32, max_dec * R, "pg_hist");
   const NgSeq ng = ng_seq(seq0, seq1, ngram, R, beam, max_dec);
+  if (wide) {
+    launch_beam_step_wide(P<int>(top_ids), P<float>(top_lp), P<float>(lp_sum), P<int>(latest), P<int>(gidx),
+                          P<int>(tok_hist), P<int>(par_hist), P<int>(done), P<int>(res_count), P<float>(res_score),
+                          P<int>(res_len), P<int>(res_step), P<int>(res_par), P<int>(step), PO<float>(att),
+                          PO<float>(att_hist), PO<float>(pg), PO<float>(pg_hist), (int)T, Na, beam, K, stop_id, min_dec,
+                          max_dec, stream(), &ng, pen);
+    return;
+  }
   launch_beam_step(P<int>(top_ids), P<float>(top_lp), P<float>(lp_sum), P<int>(latest), P<int>(gidx), P<int>(tok_hist),
                    P<int>(par_hist), P<int>(done), P<int>(res_count), P<float>(res_score), P<int>(res_len),
                    P<int>(res_step), P<int>(res_par), P<int>(step), (unsigned*)PO<int>(ctr), PO<float>(att),
@@ -1243,6 +1272,29 @@ void beam_step_pen(const Tensor& top_ids, const Tensor& top_lp, const Tensor& lp
   beam_step_run(top_ids, top_lp, lp_sum, latest, gidx, tok_hist, par_hist, done, res_count, res_score, res_len, res_step,
                 res_par, step, ctr, att, att_hist, pg, pg_hist, T, Na, beam, K, stop_id, min_dec, max_dec, seq0, seq1,
                 ng ? ngram : 0, &pen);
+}
+
+// The bookkeeping for beam sizes up to 16 (beam * K <= 512 candidates per article, one workgroup
+// of several waves each).  step was advanced by beam_gather (t = step - 1).  seq0 / seq1 / ngram:
+// n-gram blocking; inv_len (with key_sum / res_lp, optionally cpen): the penalties, off without it.
+void beam_step_wide(const Tensor& top_ids, const Tensor& top_lp, const Tensor& lp_sum, const Tensor& latest,
+                    const Tensor& gidx, const Tensor& tok_hist, const Tensor& par_hist, const Tensor& done,
+                    const Tensor& res_count, const Tensor& res_score, const Tensor& res_len, const Tensor& res_step,
+                    const Tensor& res_par, const Tensor& step, const OT& att, const OT& att_hist, const OT& pg,
+                    const OT& pg_hist, int64_t T, int64_t Na, int64_t beam, int64_t K, int64_t stop_id, int64_t min_dec,
+                    int64_t max_dec, const OT& seq0, const OT& seq1, int64_t ngram, const OT& inv_len, const OT& cpen,
+                    double beta, const OT& key_sum, const OT& res_lp) {
+  const bool ng = ngram > 1 && seq0.has_value() && seq0->defined();
+  const bool has_pen = inv_len.has_value() && inv_len->defined();
+  BeamPen pen{};
+  if (has_pen) {
+    TORCH_CHECK(key_sum.has_value() && key_sum->defined() && res_lp.has_value() && res_lp->defined(),
+                "penalties need key_sum and res_lp");
+    pen = beam_pen(*inv_len, cpen, beta, *key_sum, *res_lp, Na * beam, max_dec);
+  }
+  beam_step_run(top_ids, top_lp, lp_sum, latest, gidx, tok_hist, par_hist, done, res_count, res_score, res_len, res_step,
+                res_par, step, c10::nullopt, att, att_hist, pg, pg_hist, T, Na, beam, K, stop_id, min_dec, max_dec, seq0,
+                seq1, ng ? ngram : 0, has_pen ? &pen : nullptr, true);
 }
 
 void beam_step(const Tensor& top_ids, const Tensor& top_lp, const Tensor& lp_sum, const Tensor& latest,
@@ -1428,8 +1480,10 @@ TORCH_LIBRARY(tsamd, m) {
   m.def("clip_adagrad", &clip_adagrad);
   m.def("opt_parts", &opt_parts);
   m.def("final_topk", &final_topk);
+  m.def("final_topk_wide", &final_topk_wide);
   m.def("topk_parts", &topk_parts);
   m.def("beam_step", &beam_step);
+  m.def("beam_step_wide", &beam_step_wide);
   m.def("beam_step_ng", &beam_step_ng);
   m.def("beam_step_pen", &beam_step_pen);
   m.def("cov_penalty", &cov_penalty);

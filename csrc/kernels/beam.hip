@@ -19,7 +19,10 @@
 #include "common.h"
 #include "beam_common.h"
 
+// The candidate-list size LM of the two final_topk kernels: TOPK_MAX (K <= 16: beam <= 8) or
+// TOPK_WIDE (K <= 32: beams up to 16).  The exactness argument above holds for any K.
 #define TOPK_MAX 16
+#define TOPK_WIDE 32
 #define TOPK_THREADS 256
 
 struct Cand {
@@ -30,11 +33,12 @@ __device__ __forceinline__ bool better(float v1, int i1, float v2, int i2) { ret
 
 // Branch-light insertion into a register-resident sorted list (compile-time indices only,
 // so the list stays in VGPRs): the new candidate bubbles down through the 16 slots.
-__device__ __forceinline__ void cand_insert(Cand (&c)[TOPK_MAX], float v, int id) {
-  if (!better(v, id, c[TOPK_MAX - 1].v, c[TOPK_MAX - 1].id)) return;
+template <int LM>
+__device__ __forceinline__ void cand_insert(Cand (&c)[LM], float v, int id) {
+  if (!better(v, id, c[LM - 1].v, c[LM - 1].id)) return;
   Cand x{v, id};
 #pragma unroll
-  for (int p = 0; p < TOPK_MAX; ++p) {
+  for (int p = 0; p < LM; ++p) {
     if (better(x.v, x.id, c[p].v, c[p].id)) {
       const Cand y = c[p];
       c[p] = x;
@@ -80,9 +84,16 @@ __device__ __forceinline__ void wave_select(float* v, int* id, int n, int K, flo
 // lower bound of the true K-th largest value (the top-K thread maxima are K distinct
 // elements), so every top-K element satisfies x >= tau.  Survivors are appended to LDS
 // and the block's top-K selected from them.  Pathological ties (> FILTER_CAP survivors,
-// e.g. all-equal logits) fall back to a register bubble-insert top-K.
+// e.g. all-equal logits) fall back to a register bubble-insert top-K (LM = 16: K entries of
+// each of the 256 threads fit the FILTER_CAP staging area up to K = 8) or, for the 32-entry
+// list, to a selection in two levels that is exact for every K: a wave's 64 threads stage ALL
+// their 64 * PER_THREAD = FILTER_CAP logits, the wave's best K are selected from them, and the
+// block's best K from the 4 waves' winners (the block's top-K is within the union of the waves'
+// top-K).
 #define PER_THREAD 32
 #define FILTER_CAP 2048
+static_assert(64 * PER_THREAD <= FILTER_CAP, "one wave's logits must fit the staging area");
+template <int LM>
 __global__ __launch_bounds__(TOPK_THREADS) void final_topk_partial_kernel(
     const float* __restrict__ logits, const float* __restrict__ bias, float* __restrict__ part_ms,
     float* __restrict__ part_v, int* __restrict__ part_i, int V, int K, int per) {
@@ -91,8 +102,8 @@ __global__ __launch_bounds__(TOPK_THREADS) void final_topk_partial_kernel(
   __shared__ int si[FILTER_CAP];
   __shared__ float tmax_v[TOPK_THREADS];
   __shared__ int tmax_i[TOPK_THREADS];
-  __shared__ float selv[TOPK_MAX];
-  __shared__ int seli[TOPK_MAX];
+  __shared__ float selv[LM];
+  __shared__ int seli[LM];
   __shared__ int cnt;
   const int r = blockIdx.y, sp = blockIdx.x, tid = threadIdx.x;
   const int lo = sp * per, hi = min(V, lo + per);
@@ -148,15 +159,15 @@ __global__ __launch_bounds__(TOPK_THREADS) void final_topk_partial_kernel(
   const size_t o = ((size_t)r * gridDim.x + sp) * K;
   if (n <= FILTER_CAP) {
     if (tid < 64) wave_select(sv, si, n, K, part_v + o, part_i + o);
-  } else {  // tie-heavy fallback: exact per-thread insertion then block selection
-    Cand c[TOPK_MAX];
+  } else if constexpr (LM <= TOPK_MAX) {  // tie-heavy fallback: exact per-thread insertion then block selection
+    Cand c[LM];
 #pragma unroll
-    for (int k = 0; k < TOPK_MAX; ++k) c[k] = Cand{-INFINITY, 0x7fffffff};
+    for (int k = 0; k < LM; ++k) c[k] = Cand{-INFINITY, 0x7fffffff};
 #pragma unroll
     for (int q = 0; q < PER_THREAD; ++q) cand_insert(c, x[q], lo + ((q >> 3) * TOPK_THREADS + tid) * 8 + (q & 7));
     __syncthreads();
 #pragma unroll
-    for (int k = 0; k < TOPK_MAX; ++k) {
+    for (int k = 0; k < LM; ++k) {
       if (k < K && tid * K + k < FILTER_CAP) {
         sv[tid * K + k] = c[k].v;
         si[tid * K + k] = c[k].id;
@@ -164,6 +175,24 @@ __global__ __launch_bounds__(TOPK_THREADS) void final_topk_partial_kernel(
     }
     __syncthreads();
     if (tid < 64) wave_select(sv, si, min(TOPK_THREADS * K, FILTER_CAP), K, part_v + o, part_i + o);
+  } else {  // tie-heavy fallback, two levels: every wave's top-K of all its logits, then the block's
+    __shared__ float wv[TOPK_THREADS / 64 * LM];
+    __shared__ int wi[TOPK_THREADS / 64 * LM];
+    for (int w = 0; w < TOPK_THREADS / 64; ++w) {
+      __syncthreads();  // the staging area is free (the filter's entries, or wave w - 1's)
+      if ((tid >> 6) == w) {
+#pragma unroll
+        for (int q = 0; q < PER_THREAD; ++q) {
+          sv[(tid & 63) * PER_THREAD + q] = x[q];
+          si[(tid & 63) * PER_THREAD + q] =
+              x[q] > -INFINITY ? lo + ((q >> 3) * TOPK_THREADS + tid) * 8 + (q & 7) : 0x7fffffff;
+        }
+      }
+      __syncthreads();
+      if (tid < 64) wave_select(sv, si, 64 * PER_THREAD, K, wv + w * K, wi + w * K);
+    }
+    __syncthreads();
+    if (tid < 64) wave_select(wv, wi, TOPK_THREADS / 64 * K, K, part_v + o, part_i + o);
   }
   if (tid == 0) {
     part_ms[((size_t)r * gridDim.x + sp) * 2] = M;
@@ -176,6 +205,10 @@ __device__ __forceinline__ int hslot(int w) { return (int)(((unsigned)w * 265443
 // Pass 2, grid R: merge the TOPK_SPLIT partials (LSE + plain top-K), build the copy
 // distribution with an LDS hash table (one atomicCAS/atomicAdd per source position),
 // replace copied ids' plain values by their combined value, take the final top-K.
+// LDS: the hash, 2 * HASH_SIZE words, plus the two candidate arrays, 2 * (MAX_SPLIT * LM +
+// HASH_SIZE) words: 16 KB + 24 KB = 40 KB at LM = 16, 16 KB + 32 KB = 48 KB (+ 264 bytes of
+// small arrays) at LM = 32, under the 64 KB static limit.
+template <int LM>
 __global__ __launch_bounds__(TOPK_THREADS) void final_topk_merge_kernel(
     const float* __restrict__ part_ms, const float* __restrict__ part_v, const int* __restrict__ part_i,
     const float* __restrict__ logits, const float* __restrict__ bias, const float* __restrict__ pgen,
@@ -183,10 +216,11 @@ __global__ __launch_bounds__(TOPK_THREADS) void final_topk_merge_kernel(
     int* __restrict__ out_ids, float* __restrict__ out_lp, int V, int T, int K, int beam, int nsplit) {
   __shared__ int hkey[HASH_SIZE];
   __shared__ float hmass[HASH_SIZE];
-  __shared__ float cvv[MAX_SPLIT * TOPK_MAX + HASH_SIZE];
-  __shared__ int cii[MAX_SPLIT * TOPK_MAX + HASH_SIZE];
-  __shared__ float plain_v[TOPK_MAX];
-  __shared__ int plain_i[TOPK_MAX];
+  __shared__ float cvv[MAX_SPLIT * LM + HASH_SIZE];
+  __shared__ int cii[MAX_SPLIT * LM + HASH_SIZE];
+  static_assert(2 * HASH_SIZE * 4 + 2 * (MAX_SPLIT * LM + HASH_SIZE) * 4 + 2 * LM * 4 + 8 <= 64 * 1024, "LDS");
+  __shared__ float plain_v[LM];
+  __shared__ int plain_i[LM];
   __shared__ int ncopy;
   __shared__ float s_lse;
   const int r = blockIdx.x, tid = threadIdx.x;
@@ -340,6 +374,187 @@ __global__ __launch_bounds__(64) void beam_step_kernel(
   }
 }
 
+// ------------------------------------------------------------------ wide beams
+// beam_step_wide: the bookkeeping of beam_step_kernel / beam_step_body for up to BEAM_WIDE_CAND
+// = 16 * 32 candidates per article (beam sizes 6 to 16 with K = 2 * beam), one workgroup of
+// ceil(beam * K / 64) waves per article, thread c = candidate (hypothesis c / K, rank c % K).
+//   rank: the keys sit in LDS and every thread counts the candidates that beat its own (higher
+//     key, or the same key and a lower candidate index: the stable descending order);
+//   walk: thread p then takes rank position p.  The exclusive counts of results / new hypotheses
+//     ranked before p are a ballot + popcount within the wave plus the totals of the waves before
+//     it (LDS); p is reached iff both counts are below beam, exactly as in beam_step_body.
+// Same outputs, corner rules and trailing NgSeq / BeamPen arguments as beam_step_kernel; the step
+// counter was advanced by beam_gather (t = *step - 1).
+template <typename... NGA>
+__global__ __launch_bounds__(BEAM_WIDE_CAND) void beam_step_wide_kernel(
+    const int* __restrict__ top_ids, const float* __restrict__ top_lp,  // [R][K]
+    float* __restrict__ lp_sum, int* __restrict__ latest, int* __restrict__ gidx,  // [R]
+    int* __restrict__ tok_hist, int* __restrict__ par_hist,  // [maxD][R]
+    int* __restrict__ done, int* __restrict__ res_count,    // [Na]
+    float* __restrict__ res_score, int* __restrict__ res_len, int* __restrict__ res_step,
+    int* __restrict__ res_par,         // [Na][beam]
+    const int* __restrict__ step,
+    const float* __restrict__ att, float* __restrict__ att_hist,  // optional: [R][T] -> [maxD][R][T]
+    const float* __restrict__ pg, float* __restrict__ pg_hist,    // optional: [R] -> [maxD][R]
+    int T, int beam, int K, int stop_id, int min_dec, int max_dec, NGA... nga) {
+  constexpr bool NG = pack_has<NgSeq, NGA...>, PEN = pack_has<BeamPen, NGA...>;
+  constexpr int NWMAX = BEAM_WIDE_CAND / 64;
+  const NgSeq ng = ng_of(nga...);
+  const BeamPen pen = pen_of(nga...);
+  __shared__ __attribute__((aligned(16))) float skey[BEAM_WIDE_CAND];  // keys in candidate order
+  __shared__ float cval[BEAM_WIDE_CAND];                               // rank-ordered: raw total,
+  __shared__ int cid[BEAM_WIDE_CAND], srt[BEAM_WIDE_CAND];             // token, parent
+  __shared__ float ckey[PEN ? BEAM_WIDE_CAND : 1];                     // and key
+  __shared__ int wres[NWMAX], whyp[NWMAX], wrres[NWMAX], wrhyp[NWMAX];
+  __shared__ float nlp[BEAM_CAND_MAX], nkey[PEN ? BEAM_CAND_MAX : 1];
+  __shared__ int ntok[BEAM_CAND_MAX], npar[BEAM_CAND_MAX];
+  __shared__ __attribute__((aligned(16))) int ban[NG ? NG_BAN_MAX : 4];
+  __shared__ int adv_par[NG ? BEAM_CAND_MAX : 1], adv_tok[NG ? BEAM_CAND_MAX : 1];
+  const int a = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int nthr = (int)blockDim.x, nw = nthr >> 6;  // whole waves, nthr >= beam * K
+  const int Na = (int)gridDim.x;
+  const int base = a * beam;
+  const size_t R = (size_t)Na * beam;
+  const int t = *step - 1;
+  const int is_done = done[a], nres0 = res_count[a];
+  const int norig = t == 0 ? 1 : beam;
+  const int ncand = norig * K;
+  float tot = -INFINITY, lps = 0.f;
+  int tid_cand = 0;
+  if (tid < beam * K) {
+    const int i = tid / K, j = tid - i * K;
+    lps = lp_sum[base + i];
+    tot = lps + top_lp[(size_t)(base + i) * K + j];
+    tid_cand = top_ids[(size_t)(base + i) * K + j];
+  }
+  if (att_hist) {  // attention / p_gen history for the visualiser, row t (clamped)
+    const size_t th = (size_t)min(t, max_dec - 1);
+    for (int i = tid; i < beam * T; i += nthr) att_hist[(th * R + base) * T + i] = att[(size_t)base * T + i];
+    if (pg_hist && tid < beam) pg_hist[th * R + base + tid] = pg[base + tid];
+  }
+  if (is_done || t >= max_dec) {  // (uniform over the workgroup: the barriers below are not reached)
+    if (tid < beam) gidx[base + tid] = base + tid;
+    return;
+  }
+  if constexpr (NG) {
+    ngram_ban_build(ng.seq[t & 1], ban, base, beam, ng.P, ng.n, t, (int)R);
+    __syncthreads();
+    if (tid < beam * K && ngram_banned(ban, tid / K, ng.P, t, tid_cand)) tot = lps + BLOCKED_LP;
+  }
+  // at t == 0 only hypothesis 0's K candidates are live
+  if (tid >= ncand) tot = -INFINITY;
+  float key = tot;
+  if constexpr (PEN) key = tid < ncand ? pen_key(pen, tot, t, base + tid / K) : -INFINITY;
+  skey[tid] = key;  // threads past ncand: -inf, which beats nothing
+  __syncthreads();
+  // stable rank, four keys per LDS read (ncand rounded up to 4 stays within the workgroup's threads)
+  int rank = 0;
+  for (int q = 0; q < ncand; q += 4) {
+    const float4 v = *reinterpret_cast<const float4*>(skey + q);
+    rank += (v.x > key || (v.x == key && q < tid)) + (v.y > key || (v.y == key && q + 1 < tid)) +
+            (v.z > key || (v.z == key && q + 2 < tid)) + (v.w > key || (v.w == key && q + 3 < tid));
+  }
+  if (tid < ncand) {
+    rank = (int)DCHECK_IDX(rank, 0, ncand, CHK_BEAM_RANK);
+    cval[rank] = tot;
+    if constexpr (PEN) ckey[rank] = key;
+    cid[rank] = tid_cand;
+    srt[rank] = tid / K;
+  }
+  __syncthreads();
+  // the walk (see beam_step_body): every rank position decides at once
+  const bool act = tid < ncand;
+  const int tok = act ? cid[tid] : 0;
+  const bool is_res = act && tok == stop_id && t >= min_dec;
+  const bool is_hyp = act && tok != stop_id;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  const unsigned long long mres = __ballot(is_res), mhyp = __ballot(is_hyp);
+  if (lane == 0) {
+    wres[wid] = __popcll(mres);
+    whyp[wid] = __popcll(mhyp);
+  }
+  __syncthreads();
+  int ns = __popcll(mres & below), nn = __popcll(mhyp & below);
+  for (int w = 0; w < wid; ++w) {
+    ns += wres[w];
+    nn += whyp[w];
+  }
+  const bool reached = act && nn < beam && nres0 + ns < beam;
+  const float v = act ? cval[tid] : 0.f;
+  const int par = act ? (int)DCHECK_IDX(srt[tid], 0, norig, CHK_BEAM_PARENT) : 0;
+  if (reached && is_res) {
+    const int slot = a * beam + (int)DCHECK_IDX(nres0 + ns, 0, beam, CHK_BEAM_RANK);
+    if constexpr (PEN) {
+      res_score[slot] = ckey[tid];
+      pen.res_lp[slot] = v;
+    } else {
+      res_score[slot] = v / (float)(t + 2);
+    }
+    res_len[slot] = t + 2;
+    res_step[slot] = t;
+    res_par[slot] = par;
+  }
+  if (reached && is_hyp) {
+    const int k = (int)DCHECK_IDX(nn, 0, beam, CHK_BEAM_RANK);
+    nlp[k] = v;
+    if constexpr (PEN) nkey[k] = ckey[tid];
+    ntok[k] = tok;
+    npar[k] = par;
+  }
+  const unsigned long long mreach = __ballot(reached);
+  if (lane == 0) {
+    wrres[wid] = __popcll(mres & mreach);
+    wrhyp[wid] = __popcll(mhyp & mreach);
+  }
+  __syncthreads();
+  int nh = 0, nres = nres0;
+  for (int w = 0; w < nw; ++w) {
+    nres += wrres[w];
+    nh += wrhyp[w];
+  }
+  if (tid == 0) {
+    res_count[a] = nres;
+    if (nres >= beam) done[a] = 1;
+  }
+  if (tid < beam) {
+    const int k = tid;
+    const int kk = k < nh ? k : (nh > 0 ? nh - 1 : 0);
+    const int p = nh > 0 ? npar[kk] : 0;
+    lp_sum[base + k] = nh > 0 ? nlp[kk] : -INFINITY;
+    if constexpr (PEN) pen.key_sum[base + k] = nh > 0 ? nkey[kk] : -INFINITY;
+    latest[base + k] = nh > 0 ? ntok[kk] : stop_id;
+    gidx[base + k] = base + p;
+    tok_hist[(size_t)t * R + base + k] = nh > 0 ? ntok[kk] : stop_id;
+    par_hist[(size_t)t * R + base + k] = p;
+    if constexpr (NG) {
+      adv_par[k] = p;
+      adv_tok[k] = nh > 0 ? ntok[kk] : stop_id;
+    }
+  }
+  if constexpr (NG) {
+    __syncthreads();  // adv_par / adv_tok written by threads < beam
+    ngram_seq_advance(ng.seq[t & 1], ng.seq[(t + 1) & 1], adv_par, adv_tok, base, beam, ng.P, t, (int)R);
+  }
+}
+
+void launch_beam_step_wide(const int* top_ids, const float* top_lp, float* lp_sum, int* latest, int* gidx,
+                           int* tok_hist, int* par_hist, int* done, int* res_count, float* res_score, int* res_len,
+                           int* res_step, int* res_par, const int* step, const float* att, float* att_hist,
+                           const float* pg, float* pg_hist, int T, int Na, int beam, int K, int stop_id, int min_dec,
+                           int max_dec, hipStream_t st, const NgSeq* ng, const BeamPen* pen) {
+  const bool ngram = ng && ng->n > 1;
+  const dim3 blk((beam * K + 63) / 64 * 64);  // beam * K <= BEAM_WIDE_CAND (checked by the binding)
+#define LW(KERNEL, ...)                                                                                           \
+  hipLaunchKernelGGL(KERNEL, dim3(Na), blk, 0, st, top_ids, top_lp, lp_sum, latest, gidx, tok_hist, par_hist, done, \
+                     res_count, res_score, res_len, res_step, res_par, step, att, att_hist, pg, pg_hist, T, beam, K, \
+                     stop_id, min_dec, max_dec, ##__VA_ARGS__)
+  if (pen && ngram) LW((beam_step_wide_kernel<NgSeq, BeamPen>), *ng, *pen);
+  else if (pen) LW(beam_step_wide_kernel<BeamPen>, *pen);
+  else if (ngram) LW(beam_step_wide_kernel<NgSeq>, *ng);
+  else LW(beam_step_wide_kernel<>);
+#undef LW
+}
+
 // ------------------------------------------------------------------ coverage penalty
 // cpen[r] = sum_{i < lens[r / beam]} max(cov[r][i] + att[r][i] - 1, 0): the summary coverage
 // penalty of hypothesis row r with this step's attention included (cov: the steps before it).
@@ -432,13 +647,21 @@ int topk_split(int V) { return (V + TOPK_THREADS * PER_THREAD - 1) / (TOPK_THREA
 
 void launch_final_topk(const float* logits, const float* bias, const float* pgen, const float* attn, const int* ext,
                        const int* lens, int* out_ids, float* out_lp, float* part_ms, float* part_v, int* part_i, int R,
-                       int V, int T, int K, int beam, hipStream_t st) {
+                       int V, int T, int K, int beam, hipStream_t st, bool wide) {
   const int ns = topk_split(V);
   const int per = ((V + ns - 1) / ns + 7) / 8 * 8;
-  hipLaunchKernelGGL(final_topk_partial_kernel, dim3(ns, R), dim3(TOPK_THREADS), 0, st, logits, bias, part_ms, part_v,
-                     part_i, V, K, per);
-  hipLaunchKernelGGL(final_topk_merge_kernel, dim3(R), dim3(TOPK_THREADS), 0, st, part_ms, part_v, part_i, logits, bias,
-                     pgen, attn, ext, lens, out_ids, out_lp, V, T, K, beam, ns);
+  // wide (or K > TOPK_MAX): the kernels with the 32-entry candidate list
+  if (wide || K > TOPK_MAX) {
+    hipLaunchKernelGGL(final_topk_partial_kernel<TOPK_WIDE>, dim3(ns, R), dim3(TOPK_THREADS), 0, st, logits, bias,
+                       part_ms, part_v, part_i, V, K, per);
+    hipLaunchKernelGGL(final_topk_merge_kernel<TOPK_WIDE>, dim3(R), dim3(TOPK_THREADS), 0, st, part_ms, part_v, part_i,
+                       logits, bias, pgen, attn, ext, lens, out_ids, out_lp, V, T, K, beam, ns);
+    return;
+  }
+  hipLaunchKernelGGL(final_topk_partial_kernel<TOPK_MAX>, dim3(ns, R), dim3(TOPK_THREADS), 0, st, logits, bias, part_ms,
+                     part_v, part_i, V, K, per);
+  hipLaunchKernelGGL(final_topk_merge_kernel<TOPK_MAX>, dim3(R), dim3(TOPK_THREADS), 0, st, part_ms, part_v, part_i,
+                     logits, bias, pgen, attn, ext, lens, out_ids, out_lp, V, T, K, beam, ns);
 }
 
 void launch_beam_step(const int* top_ids, const float* top_lp, float* lp_sum, int* latest, int* gidx, int* tok_hist,

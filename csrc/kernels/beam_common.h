@@ -8,6 +8,9 @@
 #include "launchers.h"
 
 #define BEAM_CAND_MAX 16  // max beam (new hypotheses kept per step)
+// candidates per article: beam * K <= 64 in the one-wave bookkeeping (beam_step_body), up to
+// 16 * 32 in the workgroup-wide one (beam_step_wide_kernel, beam.hip)
+#define BEAM_WIDE_CAND 512
 
 // ------------------------------------------------------------------ n-gram blocking
 // block_ngram_repeat = n (decode/beam_search.py ngram_blocked): candidate w of a hypothesis with

@@ -91,7 +91,8 @@ int opt_nparts();
 
 void launch_final_topk(const float* logits, const float* bias, const float* pgen, const float* attn, const int* ext,
                        const int* lens, int* out_ids, float* out_lp, float* part_ms, float* part_v, int* part_i, int R,
-                       int V, int T, int K, int beam, hipStream_t st);
+                       int V, int T, int K, int beam, hipStream_t st, bool wide = false);
+// (wide, or K > 16: the kernels with the 32-entry candidate list, K <= 32)
 // n-gram blocking of the beam bookkeeping (beam_common.h): the hypotheses' token sequences,
 // ping-pong [R][P] each -- step t reads seq[t & 1] (tokens 0..t, [START] first) and writes
 // seq[(t + 1) & 1].  n <= 1 (or no NgSeq): off, the kernels without it run.
@@ -123,6 +124,13 @@ void launch_beam_step(const int* top_ids, const float* top_lp, float* lp_sum, in
                       int* res_par, int* step, unsigned* ctr, const float* att, float* att_hist, const float* pg,
                       float* pg_hist, int T, int Na, int beam, int K, int stop_id, int min_dec, int max_dec,
                       hipStream_t st, const NgSeq* ng = nullptr, const BeamPen* pen = nullptr);
+// the same bookkeeping for up to 16 * 32 candidates per article, one workgroup of several waves per
+// article (beam sizes 6 to 16); the step counter was advanced by launch_beam_gather
+void launch_beam_step_wide(const int* top_ids, const float* top_lp, float* lp_sum, int* latest, int* gidx,
+                           int* tok_hist, int* par_hist, int* done, int* res_count, float* res_score, int* res_len,
+                           int* res_step, int* res_par, const int* step, const float* att, float* att_hist,
+                           const float* pg, float* pg_hist, int T, int Na, int beam, int K, int stop_id, int min_dec,
+                           int max_dec, hipStream_t st, const NgSeq* ng = nullptr, const BeamPen* pen = nullptr);
 void launch_beam_gather(const int* gidx, const int* latest, const float* c_src, const bf16* h_src,
                         const float* ctx_src, const float* a_src, const float* cov_src, const float* XGtab,
                         const float* Xtab, float* c_out, bf16* h_out, float* ctx_out, bf16* ctxb_out, float* cov_out,

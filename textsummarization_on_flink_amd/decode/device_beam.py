@@ -44,13 +44,25 @@ F32 = torch.float32
 class DeviceBeamDecoder:
     pen = None  # length / coverage penalties off unless __init__ finds them in hps
 
+    MAX_BEAM = 16  # beam * 2 beam candidates per article: what the wide bookkeeping kernel ranks
+
     def __init__(self, hps, vocab, params, n_articles: int, T: int, use_graph: bool = True, chunk: int = 10,
-                 keep_attn: bool = True):
+                 keep_attn: bool = True, wide_beam: bool = False):
+        """``wide_beam``: run the wide-beam step (materialised logits, final_topk with the 32-entry
+        list, workgroup-wide bookkeeping) at any beam size; beam sizes above 5 always take it
+        (a test switch: the narrow kernels are the faster ones where they apply)."""
+        if hps.beam_size > self.MAX_BEAM:
+            raise ValueError(f"beam_size {hps.beam_size} exceeds {self.MAX_BEAM}, the largest beam the device "
+                             "decoder runs (the host beam search takes any size)")
         self.hps, self.vocab, self.p = hps, vocab, params
         self.Na, self.beam = n_articles, hps.beam_size
         self.R = self.Na * self.beam
+        # beams 1..5 (up to 64 candidates per article) run the one-wave bookkeeping and, where the
+        # shape allows, the fused select; 6..16 the unfused step with the wide kernels
+        self.wide = bool(wide_beam) or self.beam > 5
         # rows per encoder-feature row in the attention kernels (1, 2 or 4); other beam
-        # sizes fall back to replicating E/F per hypothesis
+        # sizes fall back to replicating E/F per hypothesis (wide beams with the row kernel:
+        # rep = beam, set below once the attention variant is known)
         self.rep = self.beam if self.beam in (1, 2, 4) else 1
         self.K = 2 * self.beam
         self.T = T
@@ -79,6 +91,8 @@ class DeviceBeamDecoder:
         self.k = self.eng.k
         self.row_attn = self.eng.cfg.decode_row_attn and bool(self.k.attn_row_ok(self.eng.A, T))
         self.eng.keep_ft = not self.row_attn  # the multi-block score kernel reads transposed features
+        if self.beam > 5 and self.row_attn:
+            self.rep = self.beam  # the row kernel takes any rep: an article's hypotheses share its F / E
         self.dev = self.eng.dev
         # decode_batches: up to ``group_enc`` queued plain batches are encoded as ONE
         # group_enc * n_articles-row encoder pass (the persistent LSTM's step time does not grow
@@ -133,7 +147,8 @@ class DeviceBeamDecoder:
             b[name] = z(*shape, dt=dt)
         # fused vocab head (vocab_topk.hip) partials; EngineConfig.fused_vocab_decode = False
         # selects the materialised-logits path (GEMM + final_topk) instead
-        self.fused_vocab = self.eng.cfg.fused_vocab_decode and self.K <= 8 and (self.eng.H <= 256 or self.eng.H == 512)
+        self.fused_vocab = (self.eng.cfg.fused_vocab_decode and self.K <= 8 and (self.eng.H <= 256 or self.eng.H == 512)
+                            and not self.wide)
         if self.fused_vocab:
             b["vpart_ms"] = z(R, int(self.k.vocab_topk_parts(V, H)), 2)
         # fused step (5 + 1 launches): the parent / token gathers inside the cell, x-merge and
@@ -327,8 +342,9 @@ class DeviceBeamDecoder:
                          b["logits"], b["vpart_ms"], R, V, H, T, K, self.beam)
         else:
             torch.mm(b["outb"], eng.pk["ow"], out_dtype=F32, out=b["logits"])
-            k.final_topk(b["logits"], p[OV], pg, Y["ATT"] if hps.pointer_gen else None, b["ext"], b["lens"],
-                         b["top_ids"], b["top_lp"], b["part_ms"], b["part_v"], b["part_i"], R, V, T, K, self.beam)
+            topk = k.final_topk_wide if self.wide else k.final_topk
+            topk(b["logits"], p[OV], pg, Y["ATT"] if hps.pointer_gen else None, b["ext"], b["lens"],
+                 b["top_ids"], b["top_lp"], b["part_ms"], b["part_v"], b["part_i"], R, V, T, K, self.beam)
         # beam bookkeeping; also appends a_t / p_gen to the histories (b["step"] was advanced by
         # this step's beam_gather: no grid-wide counter here)
         hist = self.keep_attn
@@ -337,7 +353,13 @@ class DeviceBeamDecoder:
                 None, Y["ATT"] if hist else None, b["ATT_hist"] if hist else None,
                 pg if (hist and pg is not None) else None, b["PG_hist"] if (hist and pg is not None) else None,
                 T, self.Na, self.beam, K, self.vocab.word2id(STOP_DECODING), hps.min_dec_steps, self.maxD)
-        if self.pen is not None:
+        if self.wide:
+            if self.pen is not None:
+                self._cov_penalty(Y)
+            seq = self.seq if self.ngram else (None, None)
+            pen = self._pen_args()[3:] if self.pen is not None else (None, None, 0.0, None, None)
+            k.beam_step_wide(*args[:14], *args[15:], seq[0], seq[1], self.ngram, *pen)  # (args[14]: no ctr)
+        elif self.pen is not None:
             self._cov_penalty(Y)
             k.beam_step_pen(*args, *self._pen_args())
         elif self.ngram:
