@@ -927,7 +927,7 @@ void vocab_topk(const Tensor& X, const Tensor& WT, const Tensor& bias, const OT&
   chk(X, BF, "X"); chk(WT, BF, "WT"); chk(bias, F32, "bias"); chk(ext, I32, "ext"); chk(lens, I32, "lens");
   chk(out_ids, I32, "out_ids"); chk(out_lp, F32, "out_lp"); chk(logits, F32, "logits"); chk(part_ms, F32, "part_ms");
   const int64_t nt = vocab_topk_tiles((int)V, (int)H);
-  TORCH_CHECK(K >= 1 && K <= 8 && beam >= 1 && R % beam == 0 && T <= 2048, "bad vocab_topk args (K <= 8)");
+  TORCH_CHECK(K >= 1 && K <= 32 && beam >= 1 && R % beam == 0 && T <= 2048, "bad vocab_topk args (1 <= K <= 32)");
   TORCH_CHECK(H % 32 == 0 && (H <= 256 || H == 512) && nt <= 4096, "vocab_topk: H % 32 == 0, H <= 256 or 512, V <= 512k");
   numel_eq(X, R * H, "X"); numel_eq(WT, V * H, "WT"); numel_eq(bias, V, "bias");
   numel_eq(ext, (R / beam) * T, "ext"); numel_eq(lens, R / beam, "lens");
@@ -951,7 +951,7 @@ void vocab_topk_pg(const Tensor& X, const Tensor& WT, const Tensor& bias, const 
   chk(ctx, F32, "ctx"); chk(c, F32, "c"); chk(h, BF, "h"); chk(x, F32, "x"); chk(pg_w, F32, "pg_w");
   chk(pg_b, F32, "pg_b"); chk(pg_out, F32, "pg_out"); chk(attn, F32, "attn");
   const int64_t nt = vocab_topk_tiles((int)V, (int)H);
-  TORCH_CHECK(K >= 1 && K <= 8 && beam >= 1 && R % beam == 0 && T <= 2048, "bad vocab_topk args (K <= 8)");
+  TORCH_CHECK(K >= 1 && K <= 32 && beam >= 1 && R % beam == 0 && T <= 2048, "bad vocab_topk args (1 <= K <= 32)");
   TORCH_CHECK(H % 32 == 0 && (H <= 256 || H == 512) && nt <= 4096, "vocab_topk: H % 32 == 0, H <= 256 or 512, V <= 512k");
   numel_eq(X, R * H, "X"); numel_eq(WT, V * H, "WT"); numel_eq(bias, V, "bias");
   numel_eq(ext, (R / beam) * T, "ext"); numel_eq(lens, R / beam, "lens");

@@ -182,6 +182,8 @@ struct PgIn {
   const float* ctx; const float* c; const bf16* h; const float* x; const float* w; const float* b; float* out;
   int A, H, E;
 };
+// K <= 8: the select kernel with 8-entry lists (optionally with the beam tail bt); 9 <= K <= 32: the
+// one with 32-entry lists, bt == nullptr
 void launch_vocab_topk(const bf16* X, const bf16* WT, const float* bias, const float* pgen, const float* attn,
                        const int* ext, const int* lens, int* out_ids, float* out_lp, float* logits, float* part_ms,
                        int R, int V, int H, int T, int K, int beam, PgIn pgi, hipStream_t st,

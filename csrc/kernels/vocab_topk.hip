@@ -19,8 +19,9 @@
 #include "launchers.h"
 
 #define VT_ROWS 64    // rows per workgroup half
-#define VT_K 8        // max K (= 2 * beam, beam <= 4)
-#define VM_CAND 4096  // tile maxima (nt <= 4096), then <= K * 256 survivors + copied ids
+#define VT_K 8        // list capacity KL of the narrow select (K = 2 * beam <= 8); the wide one holds VT_KW
+#define VT_KW 32      // K <= 32 (beams 6 to 16)
+#define VM_CAND 4096  // tile maxima (nt <= 4096), then survivors of the K best tiles, then K + copied ids
 #define VM_HASH 2048
 
 // vocab columns per workgroup: 4 MFMA column tiles per wave up to hidden 256, 2 at hidden 512
@@ -568,7 +569,16 @@ __device__ unsigned long long* vs_stamps = nullptr;
 // n-gram blocking in the beam tail (beam_common.h): instantiated with one trailing NgSeq argument
 // (without it the kernel and its arguments are exactly the plain one); its ban table reuses ci.
 // Length / coverage penalties in the beam tail: one trailing BeamPen argument, in the same way.
-template <bool STAMP = false, typename... NGA>
+//
+// KL: capacity of the top-K lists (K <= KL).  KL = 8 (beams 1 to 4) may carry the beam tail; KL = 32
+// (beams 6 to 16, bookkeeping in beam_step_wide) is instantiated without it.  Every bound below
+// (gmin, tau, tau2, theta, thr) rests on "the maxima of K disjoint groups are K distinct entries",
+// which holds for any K; with fewer than K non-empty groups a group key stays -inf and the bound
+// prunes nothing.  At KL = 32 round trip 2 reads up to 32 x 256 = 8192 logits, twice what cv / ci
+// hold: when more than VM_CAND of them survive tau2 (a row of equal logits: all do), the survivors
+// are ranked in EPT / 4 register passes of at most VM_CAND entries, each pass together with the K
+// winners so far -- top-K(A u B) = top-K(top-K(A) u B), exact for every input.
+template <bool STAMP = false, int KL = VT_K, typename... NGA>
 __global__ __launch_bounds__(VS_THREADS) void vocab_select_kernel(
     const float* __restrict__ logits, const float* __restrict__ part_ms, const float* __restrict__ pgen,
     const float* __restrict__ attn, const int* __restrict__ ext, const int* __restrict__ lens,
@@ -581,12 +591,13 @@ __global__ __launch_bounds__(VS_THREADS) void vocab_select_kernel(
   __shared__ int bt_last;
   __shared__ int hkey[VM_HASH];
   __shared__ float hmass[VM_HASH];
-  __shared__ __attribute__((aligned(16))) float cv[VM_CAND + 8];
-  __shared__ __attribute__((aligned(16))) int ci[VM_CAND + 8];
+  constexpr int CARRY = KL > VT_K ? KL : 0;  // the winners so far, in front of a pass's survivors
+  __shared__ __attribute__((aligned(16))) float cv[VM_CAND + CARRY + 8];
+  __shared__ __attribute__((aligned(16))) int ci[VM_CAND + CARRY + 8];
   __shared__ float red[16];
-  __shared__ float pv_s[3][VT_K];
-  __shared__ int pi_s[3][VT_K];
-  __shared__ int gkey[VT_K], gkey2[VT_K], gkey3[VT_K];
+  __shared__ float pv_s[3][KL];
+  __shared__ int pi_s[3][KL];
+  __shared__ int gkey[KL], gkey2[KL], gkey3[KL];
   __shared__ int ncand, ncopy;
   const int r = blockIdx.x, tid = threadIdx.x;
   const int art = r / beam;
@@ -625,9 +636,9 @@ __global__ __launch_bounds__(VS_THREADS) void vocab_select_kernel(
     ea[u] = i < len ? attn[(size_t)r * T + i] : 0.f;
   }
   for (int i = tid; i < VM_HASH; i += VS_THREADS) { hkey[i] = -1; hmass[i] = 0.f; }
-  if (tid < 3 * VT_K) { (&pv_s[0][0])[tid] = -INFINITY; (&pi_s[0][0])[tid] = VS_NONE; }
+  if (tid < 3 * KL) { (&pv_s[0][0])[tid] = -INFINITY; (&pi_s[0][0])[tid] = VS_NONE; }
   if (tid == 0) { ncand = 0; ncopy = 0; }
-  if (tid < VT_K) { gkey[tid] = okey(-INFINITY); gkey2[tid] = okey(-INFINITY); gkey3[tid] = okey(-INFINITY); }
+  if (tid < KL) { gkey[tid] = okey(-INFINITY); gkey2[tid] = okey(-INFINITY); gkey3[tid] = okey(-INFINITY); }
   float m = -INFINITY;
 #pragma unroll
   for (int u = 0; u < PPT; ++u) m = fmaxf(m, pm[u].x);
@@ -693,7 +704,7 @@ __global__ __launch_bounds__(VS_THREADS) void vocab_select_kernel(
   if (tid == 0) ncand = 0;
   const float tau = pv_s[0][K - 1];
   // ---- round trip 2: the K selected tiles' logits and the copied words' logits
-  constexpr int EPT = VT_K * 256 / VS_THREADS;  // tiles of <= 256 columns
+  constexpr int EPT = KL * 256 / VS_THREADS;  // tiles of <= 256 columns
   float zs[EPT];
   int cs[EPT];
 #pragma unroll
@@ -733,16 +744,49 @@ __global__ __launch_bounds__(VS_THREADS) void vocab_select_kernel(
   for (int u = 0; u < EPT; ++u)
     if (cs[u] < V && zs[u] >= tau2) {
       const int slot = atomicAdd(&ncand, 1);
-      cv[slot] = zs[u];
-      ci[slot] = cs[u];
+      if (KL * 256 <= VM_CAND || slot < VM_CAND) {  // (KL = 8: at most 2048 survivors, no test)
+        cv[slot] = zs[u];
+        ci[slot] = cs[u];
+      }
     }
   __syncthreads();
   const int nc = ncand;
-  pad4(cv, ci, nc);
-  __syncthreads();
-  VS_ST(8);
-  rank_select(cv, ci, (nc + 3) & ~3, K, pv_s[1], pi_s[1]);  // plain top-K
-  __syncthreads();
+  if (KL * 256 <= VM_CAND || nc <= VM_CAND) {  // uniform
+    pad4(cv, ci, nc);
+    __syncthreads();
+    VS_ST(8);
+    rank_select(cv, ci, (nc + 3) & ~3, K, pv_s[1], pi_s[1]);  // plain top-K
+    __syncthreads();
+  } else {
+    // more survivors than cv / ci hold (ties at tau2): passes over 4 registers per thread, at most
+    // VM_CAND survivors each, behind the K winners of the passes before (sentinels in pass 0).
+    // A pass ranks at least as many entries as the one before it, so it rewrites every rank that
+    // pass filled.  Need not be fast: two rank selects over ~4100 entries.
+    static_assert(EPT % 4 == 0 || KL * 256 <= VM_CAND, "passes of 4 registers");
+#pragma unroll
+    for (int h = 0; h < EPT / 4; ++h) {
+      __syncthreads();  // the appends above / the rank select of pass h - 1 are done with cv, ci
+      if (tid < K) {
+        cv[tid] = h ? pv_s[1][tid] : -INFINITY;
+        ci[tid] = h ? pi_s[1][tid] : VS_NONE;
+      }
+      if (tid == 0) ncand = 0;
+      __syncthreads();
+#pragma unroll
+      for (int u = 4 * h; u < 4 * h + 4; ++u)
+        if (cs[u] < V && zs[u] >= tau2) {
+          const int slot = K + atomicAdd(&ncand, 1);  // < K + 4 * VS_THREADS = K + VM_CAND
+          cv[slot] = zs[u];
+          ci[slot] = cs[u];
+        }
+      __syncthreads();
+      const int np = K + ncand;
+      pad4(cv, ci, np);
+      __syncthreads();
+      rank_select(cv, ci, (np + 3) & ~3, K, pv_s[1], pi_s[1]);
+    }
+    __syncthreads();
+  }
   VS_ST(9);
   // final candidates: plain top-K (copied words masked: their entry below is exact) U copied words
   if (tid < K) {
@@ -798,7 +842,7 @@ __global__ __launch_bounds__(VS_THREADS) void vocab_select_kernel(
     out_ids[(size_t)r * K + tid] = pi_s[2][tid];
     out_lp[(size_t)r * K + tid] = __logf(pv_s[2][tid]);
   }
-  if (bt.lp_sum) {  // uniform
+  if (KL == VT_K && bt.lp_sum) {  // uniform (the wide list has no beam tail)
     // this row's own p_gen history entry (the article tail must not read the p_gen of the
     // article's other rows: those are plain stores of other workgroups of this launch)
     if (tid == 0 && bt.pg_hist) {
@@ -887,15 +931,18 @@ void launch_vocab_topk(const bf16* X, const bf16* WT, const float* bias, const f
     else if (H == 256) VPL(256);
     else VPL(512);
 #undef VPL
-    if (pens && ngram)
-      hipLaunchKernelGGL((vocab_select_kernel<false, NgSeq, BeamPen>), dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms,
+    if (K > VT_K)  // beams 6 to 16: the 32-entry lists, no beam tail (the bindings refuse one)
+      hipLaunchKernelGGL((vocab_select_kernel<false, VT_KW>), dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms, pgen, attn,
+                         ext, lens, out_ids, out_lp, V, T, K, beam, nt, 16 * VP_NI * VP_WAVES, pgi, none, 1);
+    else if (pens && ngram)
+      hipLaunchKernelGGL((vocab_select_kernel<false, VT_K, NgSeq, BeamPen>), dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms,
                          pgen, attn, ext, lens, out_ids, out_lp, V, T, K, beam, nt, 16 * VP_NI * VP_WAVES, pgi, *bt, 1,
                          ngv, *pen);
     else if (pens)
-      hipLaunchKernelGGL((vocab_select_kernel<false, BeamPen>), dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms, pgen,
+      hipLaunchKernelGGL((vocab_select_kernel<false, VT_K, BeamPen>), dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms, pgen,
                          attn, ext, lens, out_ids, out_lp, V, T, K, beam, nt, 16 * VP_NI * VP_WAVES, pgi, *bt, 1, *pen);
     else if (ngram)
-      hipLaunchKernelGGL((vocab_select_kernel<false, NgSeq>), dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms, pgen, attn,
+      hipLaunchKernelGGL((vocab_select_kernel<false, VT_K, NgSeq>), dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms, pgen, attn,
                          ext, lens, out_ids, out_lp, V, T, K, beam, nt, 16 * VP_NI * VP_WAVES, pgi, *bt, 1, ngv);
     else if (vs_stamp_host)
       hipLaunchKernelGGL(vocab_select_kernel<true>, dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms, pgen, attn, ext, lens,
@@ -920,14 +967,17 @@ void launch_vocab_topk(const bf16* X, const bf16* WT, const float* bias, const f
     hipLaunchKernelGGL((vocab_logits_kernel<2, 1, 512, true>), dim3(8 * RB * ((nt + 7) / 8)), dim3(256), 0, st, X, WT,
                        bias, logits, part_ms, R, V, H);
   }
-  if (pens && ngram)
-    hipLaunchKernelGGL((vocab_select_kernel<false, NgSeq, BeamPen>), dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms,
+  if (K > VT_K)
+    hipLaunchKernelGGL((vocab_select_kernel<false, VT_KW>), dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms, pgen, attn,
+                       ext, lens, out_ids, out_lp, V, T, K, beam, nt, tcols, pgi, none, 0);
+  else if (pens && ngram)
+    hipLaunchKernelGGL((vocab_select_kernel<false, VT_K, NgSeq, BeamPen>), dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms,
                        pgen, attn, ext, lens, out_ids, out_lp, V, T, K, beam, nt, tcols, pgi, *bt, 0, ngv, *pen);
   else if (pens)
-    hipLaunchKernelGGL((vocab_select_kernel<false, BeamPen>), dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms, pgen,
+    hipLaunchKernelGGL((vocab_select_kernel<false, VT_K, BeamPen>), dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms, pgen,
                        attn, ext, lens, out_ids, out_lp, V, T, K, beam, nt, tcols, pgi, *bt, 0, *pen);
   else if (ngram)
-    hipLaunchKernelGGL((vocab_select_kernel<false, NgSeq>), dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms, pgen, attn,
+    hipLaunchKernelGGL((vocab_select_kernel<false, VT_K, NgSeq>), dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms, pgen, attn,
                        ext, lens, out_ids, out_lp, V, T, K, beam, nt, tcols, pgi, *bt, 0, ngv);
   else
     hipLaunchKernelGGL(vocab_select_kernel<false>, dim3(R), dim3(VS_THREADS), 0, st, logits, part_ms, pgen, attn, ext, lens,

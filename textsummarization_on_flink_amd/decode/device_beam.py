@@ -48,9 +48,10 @@ class DeviceBeamDecoder:
 
     def __init__(self, hps, vocab, params, n_articles: int, T: int, use_graph: bool = True, chunk: int = 10,
                  keep_attn: bool = True, wide_beam: bool = False):
-        """``wide_beam``: run the wide-beam step (materialised logits, final_topk with the 32-entry
-        list, workgroup-wide bookkeeping) at any beam size; beam sizes above 5 always take it
-        (a test switch: the narrow kernels are the faster ones where they apply)."""
+        """``wide_beam``: run the wide-beam step on materialised logits (library GEMM, final_topk with
+        the 32-entry list, workgroup-wide bookkeeping) at any beam size (a test switch: the narrow
+        kernels are the faster ones where they apply).  Beam sizes above 5 always take the wide
+        bookkeeping, by default behind the fused vocab head."""
         if hps.beam_size > self.MAX_BEAM:
             raise ValueError(f"beam_size {hps.beam_size} exceeds {self.MAX_BEAM}, the largest beam the device "
                              "decoder runs (the host beam search takes any size)")
@@ -58,8 +59,10 @@ class DeviceBeamDecoder:
         self.Na, self.beam = n_articles, hps.beam_size
         self.R = self.Na * self.beam
         # beams 1..5 (up to 64 candidates per article) run the one-wave bookkeeping and, where the
-        # shape allows, the fused select; 6..16 the unfused step with the wide kernels
-        self.wide = bool(wide_beam) or self.beam > 5
+        # shape allows, the fused select with the bookkeeping in its tail; 6..16 the unfused step with
+        # the wide bookkeeping kernel behind the fused vocab head (K <= 32) or final_topk
+        self.wide_switch = bool(wide_beam)
+        self.wide = self.wide_switch or self.beam > 5
         # rows per encoder-feature row in the attention kernels (1, 2 or 4); other beam
         # sizes fall back to replicating E/F per hypothesis (wide beams with the row kernel:
         # rep = beam, set below once the attention variant is known)
@@ -147,13 +150,19 @@ class DeviceBeamDecoder:
             b[name] = z(*shape, dt=dt)
         # fused vocab head (vocab_topk.hip) partials; EngineConfig.fused_vocab_decode = False
         # selects the materialised-logits path (GEMM + final_topk) instead
-        self.fused_vocab = (self.eng.cfg.fused_vocab_decode and self.K <= 8 and (self.eng.H <= 256 or self.eng.H == 512)
-                            and not self.wide)
+        # Beams 6 to 16 (wide by their size) take it too, with the select's 32-entry lists, in front
+        # of beam_step_wide; ``wide_beam=True`` (the test switch) keeps the materialised step at
+        # every beam size.  On by default for all of 6..16: bench_decode.py, 64 articles, V = 50k,
+        # three alternated runs each, materialised -> fused summaries/s: beam 8 2348 -> 3587,
+        # beam 10 1802 -> 2588, beam 16 915 -> 1694; with blocking and both penalties 2245 -> 3364,
+        # 1749 -> 2481, 902 -> 1646; run-to-run spread under 1.5 % (profiles/wide_beam_fused.md).
+        self.fused_vocab = (self.eng.cfg.fused_vocab_decode and (self.eng.H <= 256 or self.eng.H == 512)
+                            and (self.K <= 32 and not self.wide_switch if self.wide else self.K <= 8))
         if self.fused_vocab:
             b["vpart_ms"] = z(R, int(self.k.vocab_topk_parts(V, H)), 2)
         # fused step (5 + 1 launches): the parent / token gathers inside the cell, x-merge and
         # attention kernels, the beam bookkeeping in the vocab select kernel's tail
-        self.fused_step = self.fused_vocab and self.row_attn and self.beam * self.K <= 64
+        self.fused_step = self.fused_vocab and not self.wide and self.row_attn and self.beam * self.K <= 64
         b["art_ctr"] = z(Na, dt=torch.int32)
         b["gran"] = z(R, K, dt=torch.long)  # tagged candidate granules of the fused beam tail
         b["tail_err"] = z(1, dt=torch.int32)
