@@ -34,8 +34,9 @@ using namespace attn_rowp;
 namespace {
 
 // waves per workgroup: as many as the double-buffered rows leave registers for --
-// forward at hidden 256: 16 (<= 128 VGPRs); backward at hidden 256: 12 (<= 168 VGPRs, the
-// extra dctx / per-feature state); hidden 512 (16 features per lane): 8 (<= 256 VGPRs)
+// forward at hidden 256: 16 (<= 128 VGPRs; uses 128); backward at hidden 256: 12 (<= 168 VGPRs, the
+// extra dctx / per-feature state; uses 140); hidden 512 (16 features per lane): 8 (<= 256 VGPRs;
+// forward 223, backward 252).  None of them spills (tests/test_attn_row_resources.py).
 template <int NK, bool BWD>
 constexpr int row_waves() { return NK == 1 ? (BWD ? 12 : 16) : 8; }
 
@@ -585,8 +586,9 @@ bool attn_row_supported(int A, int T) { return (A == 512 || A == 1024) && T >= 1
 bool attn_rowp_supported(int A, int T, int EG) { return attn_row_supported(A, T) && EG == kEG; }
 
 // waves per workgroup of the projected kernels: forward 16 / 8 (A = 512 / 1024) as row_waves();
-// backward 16 at A = 512 (128 VGPRs, 2 spilled: B = 256 17.47-17.51 -> 17.22 ms per step against
-// 12 waves, 17.75 with 8) and 8 at A = 1024 (4 equal, 12 spills 75; profiles/r3/ab/rowp_waves.txt)
+// backward 16 at A = 512 (122 VGPRs, none spilled: B = 256 17.47-17.51 -> 17.22 ms per step against
+// 12 waves, 17.75 with 8) and 8 at A = 1024 (198 VGPRs, none spilled; 4 waves equal, 12 spilled when
+// measured; profiles/r3/ab/rowp_waves.txt).  tests/test_attn_row_resources.py holds the register figures.
 template <int NK>
 constexpr int rowp_bwd_waves() { return NK == 1 ? 16 : 8; }
 
