@@ -277,6 +277,59 @@ void dec_fwd_persistent(const Tensor& XG, const Tensor& KcT, const Tensor& WsT, 
                             stream());
 }
 
+// persistent decoder backward loop: all D steps of attn_bwd_rowp -> dec_bwd_cell -> dec_bwd_dz in one launch
+// (decoder_bwd_persistent.hip).  dh_rec / dc_carry hold the loop's start values and receive its final ones.
+// The caller zeroes xbuf before every launch.
+int64_t dec_bwd_persistent_capacity_op() { return dec_bwd_persistent_capacity(); }
+int64_t dec_bwd_persistent_xbuf_op(int64_t B) { return (int64_t)dec_bwd_persistent_xbuf_elems((int)B); }
+void dec_bwd_persistent(const Tensor& G, const Tensor& F, const Tensor& S, const Tensor& v, const OT& wc, const OT& COV,
+                        const Tensor& ATT, const Tensor& GV, const Tensor& Ga, const OT& gcl, const Tensor& lens,
+                        const Tensor& DE, const Tensor& DS, const Tensor& Ws, const OT& dC_dir, const Tensor& dH_dir,
+                        const Tensor& dh_rec, const Tensor& dc_carry, const Tensor& ACT, const Tensor& Cst,
+                        const Tensor& DZ, const Tensor& Kc, const OT& dX_dir, const Tensor& DX, const OT& dlen,
+                        const Tensor& xbuf, const Tensor& err, int64_t B, int64_t T, int64_t D, int64_t H, int64_t E,
+                        int64_t A) {
+  TORCH_CHECK(dec_persistent_shape_ok((int)H, (int)E, (int)A, (int)B, (int)T) && D >= 1,
+              "dec_bwd_persistent: unsupported shape");
+  const int64_t grid = dec_persistent_grid((int)B);
+  TORCH_CHECK(grid > 0 && grid <= dec_bwd_persistent_capacity(),
+              "dec_bwd_persistent: the grid would not be co-resident on this device");
+  chk(G, BF, "G"); numel_eq(G, B * T * E, "G");
+  chk(F, BF, "F"); numel_eq(F, B * T * A, "F");
+  chk(S, F32, "S"); numel_eq(S, D * B * A, "S");
+  chk(v, F32, "v"); numel_eq(v, A, "v");
+  chko(wc, F32, A, "wc");
+  chko(COV, F32, (D + 1) * B * T, "COV");
+  chk(ATT, F32, "ATT"); numel_eq(ATT, D * B * T, "ATT");
+  chk(GV, F32, "GV"); numel_eq(GV, D * B * E, "GV");
+  chk(Ga, F32, "Ga"); numel_eq(Ga, D * B * T, "Ga");
+  chko(gcl, F32, D * B, "gcl");
+  TORCH_CHECK((PO<float>(COV) != nullptr) == (PO<float>(gcl) != nullptr), "COV and gcl go together");
+  chk(lens, I32, "lens"); numel_eq(lens, B, "lens");
+  chk(DE, F32, "DE"); numel_eq(DE, D * B * T, "DE");
+  chk(DS, F32, "DS"); numel_eq(DS, D * B * A, "DS");
+  chk(Ws, BF, "Ws"); numel_eq(Ws, 2 * H * A, "Ws");
+  chko(dC_dir, F32, D * B * H, "dC_dir");
+  chk(dH_dir, F32, "dH_dir"); numel_eq(dH_dir, D * B * H, "dH_dir");
+  chk(dh_rec, F32, "dh_rec"); numel_eq(dh_rec, B * H, "dh_rec");
+  chk(dc_carry, F32, "dc_carry"); numel_eq(dc_carry, B * H, "dc_carry");
+  chk(ACT, F32, "ACT"); numel_eq(ACT, D * B * 4 * H, "ACT");
+  chk(Cst, F32, "Cst"); numel_eq(Cst, (D + 1) * B * H, "Cst");
+  chk(DZ, BF, "DZ"); numel_eq(DZ, D * B * 4 * H, "DZ");
+  chk(Kc, BF, "Kc"); numel_eq(Kc, (E + H) * 4 * H, "Kc");
+  chko(dX_dir, F32, D * B * E, "dX_dir");
+  chk(DX, F32, "DX"); numel_eq(DX, D * B * E, "DX");
+  chko(dlen, I32, B, "dlen");
+  chk(xbuf, at::kLong, "xbuf"); numel_eq(xbuf, (int64_t)dec_bwd_persistent_xbuf_elems((int)B), "xbuf");
+  chk(err, I32, "err");
+  launch_dec_bwd_persistent(P<bf16>(G), P<bf16>(F), P<float>(S), P<float>(v), PO<float>(wc), PO<float>(COV),
+                            P<float>(ATT), P<float>(GV), P<float>(Ga), PO<float>(gcl), P<int>(lens), P<float>(DE),
+                            P<float>(DS), P<bf16>(Ws), PO<float>(dC_dir), P<float>(dH_dir), P<float>(dh_rec),
+                            P<float>(dc_carry), P<float>(ACT), P<float>(Cst), P<bf16>(DZ), P<bf16>(Kc),
+                            PO<float>(dX_dir), P<float>(DX), PO<int>(dlen), (unsigned long long*)xbuf.data_ptr(),
+                            (unsigned*)err.data_ptr(), (int)B, (int)T, (int)D, stream());
+}
+
 void attn_fwd_rowp(const Tensor& F, const Tensor& G, const Tensor& s, const Tensor& v, const OT& wc, const OT& cov,
                    const Tensor& lens, const Tensor& a_out, const OT& cov_out, const OT& covloss, const Tensor& gx,
                    const Tensor& gx_bf, int64_t B, int64_t T, int64_t A, const OT& dlen, int64_t step,
@@ -1430,6 +1483,9 @@ TORCH_LIBRARY(tsamd, m) {
   m.def("dec_persistent_xbuf", &dec_persistent_xbuf_op);
   m.def("dec_persistent_stamps", &dec_persistent_stamps_op);
   m.def("dec_fwd_persistent", &dec_fwd_persistent);
+  m.def("dec_bwd_persistent_capacity", &dec_bwd_persistent_capacity_op);
+  m.def("dec_bwd_persistent_xbuf", &dec_bwd_persistent_xbuf_op);
+  m.def("dec_bwd_persistent", &dec_bwd_persistent);
   m.def("attn_bwd_rowp", &attn_bwd_rowp);
   m.def("attn_bwd_feat", &attn_bwd_feat);
   m.def("attn_chunks", &attn_chunks);

@@ -69,6 +69,16 @@ void launch_dec_fwd_persistent(const float* XG, const bf16* KcT, const bf16* WsT
                                const float* wc, float* COV, const int* lens, float* ATT, bf16* ATTb, float* covloss,
                                float* GV, bf16* GVb, const int* dlen, unsigned long long* xbuf, unsigned* err, int B,
                                int T, int D, hipStream_t st);
+// persistent decoder backward loop (decoder_bwd_persistent.hip): all D steps of the reverse chain in one
+// launch; shape rule and grid are the forward's (dec_persistent_shape_ok, dec_persistent_grid)
+int dec_bwd_persistent_capacity();
+size_t dec_bwd_persistent_xbuf_elems(int B);
+void launch_dec_bwd_persistent(const bf16* G, const bf16* F, const float* S, const float* v, const float* wc,
+                               const float* COV, const float* ATT, const float* GV, const float* Ga, const float* gcl,
+                               const int* lens, float* DE, float* DS, const bf16* Ws, const float* dC_dir,
+                               const float* dH_dir, float* dh_rec, float* dc_carry, const float* ACT, const float* Cst,
+                               bf16* DZ, const bf16* Kc, const float* dX_dir, float* DX, const int* dlen,
+                               unsigned long long* xbuf, unsigned* err, int B, int T, int D, hipStream_t st);
 void launch_dec_bwd_cell(const float* ds, const bf16* Ws, const float* dC_dir, const float* dH_dir,
                          const float* dh_rec, float* dc_carry, const float* act, const float* c_now,
                          const float* c_prev, bf16* dz, int B, int H, int A, const int* dlen, int step,

@@ -9,6 +9,7 @@ engine is built); code can also pass a config explicitly.
 |---------------------------|--------------------|-------------------|
 | TSAMD_LSTM_PERSISTENT     | persistent_lstm    | 1: one persistent weight-resident launch per bi-LSTM pass; 0: per-step kernels |
 | TSAMD_DEC_PERSISTENT      | dec_persistent     | 1: the decoder forward loop as one persistent launch with per-tile hand-offs when ``dec_persistent_eligible`` (hidden 256, emb 128, projected row attention, B % 16 == 0, the whole grid co-resident); 0 or not eligible: three launches per step and row group |
+| TSAMD_DEC_BWD_PERSISTENT  | dec_bwd_persistent | 1: the decoder backward loop as one persistent launch with per-tile hand-offs when ``dec_bwd_persistent_eligible`` (the forward's shape and capacity rule, and no vocab-dW side stream beside the loop); 0 or not eligible: three launches per step and row group |
 | TSAMD_ROW_ATTN            | row_attn           | auto (B >= 64): one workgroup per row; 0 / 1 force |
 | TSAMD_SPLIT               | split              | auto (2 groups from B = 256, 4 from B = 1024): decoder row groups on parallel streams (forward loop: only when the persistent decoder launch is off or not eligible) |
 | TSAMD_SPLIT_BWD           | split_bwd          | auto (= split): row groups of the decoder backward loop |
@@ -43,6 +44,7 @@ def _tri(env: Mapping[str, str], name: str) -> Optional[bool]:
 class EngineConfig:
     persistent_lstm: bool = True
     dec_persistent: bool = True
+    dec_bwd_persistent: bool = True
     row_attn: Optional[bool] = None
     split: int = 0
     split_bwd: int = 0
@@ -61,6 +63,7 @@ class EngineConfig:
         cfg = cls(
             persistent_lstm=_flag(env, "TSAMD_LSTM_PERSISTENT", True),
             dec_persistent=_flag(env, "TSAMD_DEC_PERSISTENT", True),
+            dec_bwd_persistent=_flag(env, "TSAMD_DEC_BWD_PERSISTENT", True),
             row_attn=_tri(env, "TSAMD_ROW_ATTN"),
             split=int(env.get("TSAMD_SPLIT", "0") or 0),
             split_bwd=int(env.get("TSAMD_SPLIT_BWD", "0") or 0),
@@ -114,3 +117,24 @@ def dec_persistent_eligible(H: int, E: int, A: int, B: int, T: int, proj_attn: b
     grid = dec_persistent_grid(B)
     cap = capacity - (reserve_cus if world > 1 else 0)
     return 0 < grid <= cap
+
+
+def dec_bwd_persistent_eligible(H: int, E: int, A: int, B: int, T: int, proj_attn: bool, row_attn: bool,
+                                world: int = 1, capacity: int = 0, reserve_cus: int = 0,
+                                dw_side: bool = False) -> bool:
+    """Whether the decoder backward loop may run as ONE persistent launch
+    (csrc/kernels/decoder_bwd_persistent.hip): the forward's shape and capacity rule, with
+    ``capacity`` the occupancy query of the backward kernel, plus what may hold a CU beside the
+    loop in the backward phase it runs in:
+
+    * the vocab dW side stream (``dw_side``: the graph trainer's TSAMD_VOCAB_DW_SIDE) runs a GEMM
+      beside the loop, so the launch is not eligible with it;
+    * with more than one rank, bucket 0's all-reduce overlaps this phase, so ``reserve_cus`` comes
+      off the capacity exactly as for the forward;
+    * weight gradients that are not deferred run before the loop on the same stream, and the
+      deferred ones start after it (they wait for the main stream), so neither holds a CU beside it.
+
+    Not eligible means the three-kernel chains, never an error."""
+    if dw_side:
+        return False
+    return dec_persistent_eligible(H, E, A, B, T, proj_attn, row_attn, world, capacity, reserve_cus)

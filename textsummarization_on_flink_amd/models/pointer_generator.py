@@ -30,7 +30,7 @@ import torch
 
 from ..ops import ops as _ops
 from ..parallel.rccl_env import rccl_cu_reserve
-from .engine_config import EngineConfig, dec_persistent_eligible
+from .engine_config import EngineConfig, dec_bwd_persistent_eligible, dec_persistent_eligible
 from .params import DEC, P, FlatParams, enc_prefix
 
 BF = torch.bfloat16
@@ -711,6 +711,23 @@ class HipPointerGenerator:
             rccl_cu_reserve())
         if self.dec_persistent and getattr(self, "_dec_xbuf", None) is None:
             self._dec_xbuf = torch.zeros(int(k.dec_persistent_xbuf(self.B)), dtype=torch.long, device=self.dev)
+        # the backward loop likewise (decoder_bwd_persistent.hip); the vocab-dW side stream is known only
+        # when the trainer has set split_vocab_dw, so dec_bwd_persistent_on() decides at call time
+        self._dec_bwd_cap = int(k.dec_bwd_persistent_capacity()) if (self.cfg.dec_bwd_persistent and self.proj_attn) else 0
+        # the hand-off buffer exists whenever the device admits the kernel and the batch is whole tiles, i.e.
+        # for every world size / side-stream setting that dec_bwd_persistent_on() may later see (it is
+        # not allocated at the call site: that may be inside a graph capture)
+        if self._dec_bwd_cap > 0 and self.B >= 16 and self.B % 16 == 0 and getattr(self, "_dec_bwd_xbuf", None) is None:
+            self._dec_bwd_xbuf = torch.zeros(int(k.dec_bwd_persistent_xbuf(self.B)), dtype=torch.long, device=self.dev)
+
+    # tools/phase_micro.py sets this to time backward_mid with the chains on an engine that is eligible
+    dec_bwd_force_chains = False
+
+    def dec_bwd_persistent_on(self) -> bool:
+        """Whether _backward_mid_proj runs the reverse loop as the one persistent launch."""
+        return self.cfg.dec_bwd_persistent and not self.dec_bwd_force_chains and dec_bwd_persistent_eligible(
+            self.H, self.E, self.A, self.B, self.T, self.proj_attn, self.row_attn, self.world, self._dec_bwd_cap,
+            rccl_cu_reserve(), dw_side=bool(getattr(self, "split_vocab_dw", False)))
 
     def set_world(self, world: int) -> None:
         """Data-parallel trainers: RCCL collectives of ``world`` > 1 ranks may hold CUs, which come
@@ -721,13 +738,17 @@ class HipPointerGenerator:
     def check_lstm_err(self) -> None:
         """Host sync: raise if a hand-off of a persistent kernel timed out in any launch since the
         engine was built: the persistent LSTM (codes 1 forward, 2 BPTT) or the persistent decoder
-        forward loop (code 3), which share the word.  It is sticky: those results were garbage, the
+        forward / backward loop (codes 3 / 4), which share the word.  It is sticky: those results were garbage, the
         optimizer kernel skipped the update, and eval / decode must not report them."""
         code = int(self.w["lstm_err"].item())
         if code == 3:
             raise LstmHandoffError("persistent decoder forward hand-off timed out (code 3: a workgroup was not "
                                    "co-resident); results of that launch were discarded -- set "
                                    "TSAMD_DEC_PERSISTENT=0 (EngineConfig.dec_persistent)")
+        if code == 4:
+            raise LstmHandoffError("persistent decoder backward hand-off timed out (code 4: a workgroup was not "
+                                   "co-resident); results of that launch were discarded -- set "
+                                   "TSAMD_DEC_BWD_PERSISTENT=0 (EngineConfig.dec_bwd_persistent)")
         if code:
             raise LstmHandoffError(f"persistent LSTM hand-off timed out (code {code}: a workgroup was not "
                                    "co-resident); results of that launch were discarded -- set "
@@ -1476,7 +1497,14 @@ class HipPointerGenerator:
                 k.dec_bwd_dz(w["DZ"][t][rs], Kc, dX_dir[t][rs] if dX_dir is not None else None, None,
                              w["DX"][t][rs], None, w["dh_rec"][rs], Bg, E, H, 0, dl, t)
 
-        self._row_groups(chain, self.split_bwd)
+        if self.dec_bwd_persistent_on():
+            self._dec_bwd_xbuf.zero_()  # hand-off tags must start at 0 every launch
+            k.dec_bwd_persistent(G, F, w["S"], v, wc, w["COV"] if cov else None, w["ATT"], w["GV"], Ga,
+                                 w["gcl"] if cov else None, lens, w["DE"], w["DS"], self.pk["Ws"], dC_dir, dH_dir,
+                                 w["dh_rec"], w["dc_carry"], w["ACT"], w["Cst"], w["DZ"], Kc, dX_dir, w["DX"], dlen,
+                                 self._dec_bwd_xbuf, w["lstm_err"], B, T, D, H, E, A)
+        else:
+            self._row_groups(chain, self.split_bwd)
         if dCTX_dir is not w["DCTX"]:
             w["DCTX"].copy_(dCTX_dir)
         if D > 1:

@@ -11,7 +11,12 @@ is timed after the step's phases, behind a second encoder forward so both decode
 from the same cache state, and is not part of ``total``.  ``decoder_fwd_queued`` is the persistent
 decoder phase timed the same way right after it: both are enqueued while the GPU still works on the
 step, so neither contains the host's graph-launch time, which ``decoder_fwd`` (second phase after
-an idle GPU) can.
+an idle GPU) can.  Likewise for the decoder backward loop (``dec_bwd_persistent``:
+TSAMD_DEC_BWD_PERSISTENT, eligible shape): ``backward_mid_chains`` is backward_mid with the switch
+off (``dec_bwd_force_chains`` on the engine) and ``backward_mid_queued`` the persistent one, each
+timed behind a replay of backward_head.  These extra replays come after the step's optimizer phase,
+so they work on the updated weights and on gradient buffers the step has already consumed: the
+same shapes, lengths and dead steps, hence the same time, but their outputs mean nothing.
 
   python tools/phase_micro.py [--batch B] [--hidden H] [--enc T] [--layers L]
 """
@@ -65,6 +70,18 @@ def main():
 
     if eng.dec_persistent:
         phases.append(("decoder_fwd_chains", decoder_fwd_chains))
+    bwd_persistent = bool(eng.dec_bwd_persistent_on())
+
+    def backward_mid_chains():
+        eng.dec_bwd_force_chains = True
+        try:
+            eng.backward_mid()
+        finally:
+            eng.dec_bwd_force_chains = False
+
+    n_bwd = len(phases)  # index of backward_mid_chains when present
+    if bwd_persistent:
+        phases.append(("backward_mid_chains", backward_mid_chains))
     graphs = []
     pool = torch.cuda.graph_pool_handle()
     s = torch.cuda.Stream()
@@ -83,7 +100,9 @@ def main():
             graphs.append(g)
     torch.cuda.synchronize()
     res = {"batch": a.batch, "hidden": a.hidden, "enc": a.enc, "layers": a.layers,
-           "dec_persistent": bool(eng.dec_persistent)}
+           "dec_persistent": bool(eng.dec_persistent), "dec_bwd_persistent": bwd_persistent}
+    ev_b = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    tot_b = [0.0, 0.0]
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(phases) + 1)]
     ev_x = torch.cuda.Event(enable_timing=True)
     ev_y, tot_y = [torch.cuda.Event(enable_timing=True) for _ in range(2)], 0.0
@@ -93,7 +112,16 @@ def main():
         for i, g in enumerate(graphs[:nstep]):
             g.replay()
             ev[i + 1].record()
-        if len(phases) > nstep:  # the chains right after an encoder forward, as the persistent launch above
+        if bwd_persistent:  # backward_mid both ways, each right after a backward_head
+            graphs[3].replay()
+            ev_b[0].record()
+            graphs[n_bwd].replay()
+            ev_b[1].record()
+            graphs[3].replay()
+            ev_b[2].record()
+            graphs[4].replay()
+            ev_b[3].record()
+        if eng.dec_persistent:  # the chains right after an encoder forward, as the persistent launch above
             graphs[0].replay()
             ev_x.record()
             graphs[nstep].replay()
@@ -105,13 +133,19 @@ def main():
         torch.cuda.synchronize()
         for i in range(nstep):
             tot[i] += ev[i].elapsed_time(ev[i + 1])
-        if len(phases) > nstep:
+        if eng.dec_persistent:
             tot[nstep] += ev_x.elapsed_time(ev[nstep + 1])
             tot_y += ev_y[0].elapsed_time(ev_y[1])
-    for (n, _), t in zip(phases, tot):
+        if bwd_persistent:
+            tot_b[0] += ev_b[0].elapsed_time(ev_b[1])
+            tot_b[1] += ev_b[2].elapsed_time(ev_b[3])
+    for (n, _), t in zip(phases[:nstep + (1 if eng.dec_persistent else 0)], tot):
         res[n] = round(t / a.iters, 3)
-    if len(phases) > nstep:
+    if eng.dec_persistent:
         res["decoder_fwd_queued"] = round(tot_y / a.iters, 3)
+    if bwd_persistent:
+        res["backward_mid_chains"] = round(tot_b[0] / a.iters, 3)
+        res["backward_mid_queued"] = round(tot_b[1] / a.iters, 3)
     res["total"] = round(sum(tot[:nstep]) / a.iters, 3)
     print(json.dumps(res), flush=True)
 
