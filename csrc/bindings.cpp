@@ -234,17 +234,23 @@ int64_t dec_persistent_stamps_op(const OT& buf, int64_t B, int64_t D) {
   TORCH_CHECK(n > 0, "dec_persistent_stamps: this library was built without -DTSAMD_DEC_STAMPS");
   return n;
 }
+// both persistent decoder ops open with these: shape rule, co-resident grid, hand-off buffer, error word
+static void dec_persistent_checks(const char* op, int capacity, int64_t H, int64_t E, int64_t A, int64_t B, int64_t T,
+                                  int64_t D, const Tensor& xbuf, size_t xbuf_elems, const Tensor& err) {
+  TORCH_CHECK(dec_persistent_shape_ok((int)H, (int)E, (int)A, (int)B, (int)T) && D >= 1, op, ": unsupported shape");
+  const int64_t grid = dec_persistent_grid((int)B);
+  TORCH_CHECK(grid > 0 && grid <= capacity, op, ": the grid would not be co-resident on this device");
+  chk(xbuf, at::kLong, "xbuf"); numel_eq(xbuf, (int64_t)xbuf_elems, "xbuf");
+  chk(err, I32, "err");
+}
 void dec_fwd_persistent(const Tensor& XG, const Tensor& KcT, const Tensor& WsT, const Tensor& bs, const Tensor& Cst,
                         const Tensor& Cb, const Tensor& Hb, const Tensor& ACT, const Tensor& S, const Tensor& F,
                         const Tensor& G, const Tensor& v, const OT& wc, const OT& COV, const Tensor& lens,
                         const Tensor& ATT, const Tensor& ATTb, const OT& covloss, const Tensor& GV, const Tensor& GVb,
                         const OT& dlen, const Tensor& xbuf, const Tensor& err, int64_t B, int64_t T, int64_t D,
                         int64_t H, int64_t E, int64_t A) {
-  TORCH_CHECK(dec_persistent_shape_ok((int)H, (int)E, (int)A, (int)B, (int)T) && D >= 1,
-              "dec_fwd_persistent: unsupported shape");
-  const int64_t grid = dec_persistent_grid((int)B);
-  TORCH_CHECK(grid > 0 && grid <= dec_persistent_capacity(),
-              "dec_fwd_persistent: the grid would not be co-resident on this device");
+  dec_persistent_checks("dec_fwd_persistent", dec_persistent_capacity(), H, E, A, B, T, D, xbuf,
+                        dec_persistent_xbuf_elems((int)B), err);
   chk(XG, F32, "XG"); numel_eq(XG, D * B * 4 * H, "XG");
   chk(KcT, BF, "KcT"); numel_eq(KcT, 4 * H * (E + H), "KcT");
   chk(WsT, BF, "WsT"); numel_eq(WsT, A * 2 * H, "WsT");
@@ -267,8 +273,6 @@ void dec_fwd_persistent(const Tensor& XG, const Tensor& KcT, const Tensor& WsT, 
   chk(GV, F32, "GV"); numel_eq(GV, D * B * E, "GV");
   chk(GVb, BF, "GVb"); numel_eq(GVb, D * B * E, "GVb");
   chko(dlen, I32, B, "dlen");
-  chk(xbuf, at::kLong, "xbuf"); numel_eq(xbuf, (int64_t)dec_persistent_xbuf_elems((int)B), "xbuf");
-  chk(err, I32, "err");
   launch_dec_fwd_persistent(P<float>(XG), P<bf16>(KcT), P<bf16>(WsT), P<float>(bs), P<float>(Cst), P<bf16>(Cb),
                             P<bf16>(Hb), P<float>(ACT), P<float>(S), P<bf16>(F), P<bf16>(G), P<float>(v),
                             PO<float>(wc), PO<float>(COV), P<int>(lens), P<float>(ATT), P<bf16>(ATTb),
@@ -289,11 +293,8 @@ void dec_bwd_persistent(const Tensor& G, const Tensor& F, const Tensor& S, const
                         const Tensor& DZ, const Tensor& Kc, const OT& dX_dir, const Tensor& DX, const OT& dlen,
                         const Tensor& xbuf, const Tensor& err, int64_t B, int64_t T, int64_t D, int64_t H, int64_t E,
                         int64_t A) {
-  TORCH_CHECK(dec_persistent_shape_ok((int)H, (int)E, (int)A, (int)B, (int)T) && D >= 1,
-              "dec_bwd_persistent: unsupported shape");
-  const int64_t grid = dec_persistent_grid((int)B);
-  TORCH_CHECK(grid > 0 && grid <= dec_bwd_persistent_capacity(),
-              "dec_bwd_persistent: the grid would not be co-resident on this device");
+  dec_persistent_checks("dec_bwd_persistent", dec_bwd_persistent_capacity(), H, E, A, B, T, D, xbuf,
+                        dec_bwd_persistent_xbuf_elems((int)B), err);
   chk(G, BF, "G"); numel_eq(G, B * T * E, "G");
   chk(F, BF, "F"); numel_eq(F, B * T * A, "F");
   chk(S, F32, "S"); numel_eq(S, D * B * A, "S");
@@ -320,8 +321,6 @@ void dec_bwd_persistent(const Tensor& G, const Tensor& F, const Tensor& S, const
   chko(dX_dir, F32, D * B * E, "dX_dir");
   chk(DX, F32, "DX"); numel_eq(DX, D * B * E, "DX");
   chko(dlen, I32, B, "dlen");
-  chk(xbuf, at::kLong, "xbuf"); numel_eq(xbuf, (int64_t)dec_bwd_persistent_xbuf_elems((int)B), "xbuf");
-  chk(err, I32, "err");
   launch_dec_bwd_persistent(P<bf16>(G), P<bf16>(F), P<float>(S), P<float>(v), PO<float>(wc), PO<float>(COV),
                             P<float>(ATT), P<float>(GV), P<float>(Ga), PO<float>(gcl), P<int>(lens), P<float>(DE),
                             P<float>(DS), P<bf16>(Ws), PO<float>(dC_dir), P<float>(dH_dir), P<float>(dh_rec),

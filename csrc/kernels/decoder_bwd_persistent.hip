@@ -14,7 +14,7 @@
 // Three hand-offs per step stay inside the team (tagged 8-byte granules, two slots by step
 // parity, zeroed before every launch): ds_t (16 x 512 as bf16 pairs: dec_bwd_cell converts ds with
 // f2bf anyway), dz_t (16 x 4H as bf16 pairs) and dx_t (16 x 128 fp32, row i read by member i alone).
-// Every wait is bounded (sweep): a timeout records code 4 in *err and the grid drains.
+// Every wait is bounded (sweep): a timeout records kErrDecBwd in *err and the grid drains.
 // Order of step t (t from D - 1 down) in one workgroup (P = publish, W = sweep, st = plain stores):
 //   W dx_{t+1} (own row) | first F / G loads | st DS DZ DX of step t + 1 | position loop (st DE_t) |
 //   P ds_t | W ds_t | s-projection + cell backward | P dz_t | W dz_t | dh tile, dx tile | P dx_t
@@ -52,7 +52,6 @@
 #include "attn_rowp_fwd.h"
 #include "handoff.h"
 #include "launchers.h"
-#include <mutex>
 
 using namespace attn_rowp;
 using namespace handoff;
@@ -119,18 +118,7 @@ struct DecBwdPersistentArgs {
 
 namespace {
 
-// The kernel's arguments and the thread index, opaque per phase (see decoder_persistent.hip).
-typedef const DecBwdPersistentArgs __attribute__((address_space(4))) KArgs;
-__device__ __forceinline__ KArgs* phase_args() {
-  KArgs* a = (KArgs*)__builtin_amdgcn_kernarg_segment_ptr();  // the struct is the only argument
-  asm volatile("" : "+s"(a));
-  return a;
-}
-__device__ __forceinline__ int phase_tid() {
-  int t = threadIdx.x;
-  asm volatile("" : "+v"(t));
-  return t;
-}
+typedef const DecBwdPersistentArgs __attribute__((address_space(4))) KArgs;  // see phase_args (handoff.h)
 
 struct Scal {
   float a, r, c, dn;
@@ -187,7 +175,7 @@ __global__ __launch_bounds__(kNT) void dec_bwd_persistent_kernel(DecBwdPersisten
   }
   // ---- the tile's dead steps: the zeros of attn_bwd_rowp, dec_bwd_cell and dec_bwd_dz
   for (int t = D - 1; t >= tile_last; --t) {
-    KArgs* a = phase_args();
+    KArgs* a = phase_args<DecBwdPersistentArgs>();
     const int tid = phase_tid(), wid = tid >> 6, lane = tid & 63;
     const int row = (lane >> 4) * 4 + (wid & 3), l15 = lane & 15;
     if (wid < 4) {
@@ -203,7 +191,7 @@ __global__ __launch_bounds__(kNT) void dec_bwd_persistent_kernel(DecBwdPersisten
   // the steps at which this row is dead in a live tile: its DE zeros are known now, and written here
   // they do not stand between a ds publish and the following sweep
   for (int t = min(tile_last, D) - 1; t >= max(row_last, 0); --t) {
-    KArgs* a = phase_args();
+    KArgs* a = phase_args<DecBwdPersistentArgs>();
     const int tid = phase_tid();
     float* de = a->DE + ((size_t)t * B + b) * T;
     for (int i = tid; i < T; i += kNT) de[i] = 0.f;
@@ -216,7 +204,7 @@ __global__ __launch_bounds__(kNT) void dec_bwd_persistent_kernel(DecBwdPersisten
   unsigned st_dz0 = 0u, st_dz1 = 0u;
   auto flush = [&]() {
     if (st_t < 0) return;
-    KArgs* a = phase_args();
+    KArgs* a = phase_args<DecBwdPersistentArgs>();
     const int tid = phase_tid(), wid = tid >> 6, lane = tid & 63;
     const int row = (lane >> 4) * 4 + (wid & 3), l15 = lane & 15;
     if (tid < kA) a->DS[((size_t)st_t * B + b) * kA + tid] = st_ds;
@@ -238,7 +226,7 @@ __global__ __launch_bounds__(kNT) void dec_bwd_persistent_kernel(DecBwdPersisten
     float ds_val = 0.f;  // ds_t[b][tid], tid < 512
     // ---- attention backward of row j
     if (t < row_last) {
-      KArgs* a = phase_args();
+      KArgs* a = phase_args<DecBwdPersistentArgs>();
       const int tid = phase_tid(), wid = tid >> 6, lane = tid & 63;
       gu64* tb = a->xbuf + (size_t)team * kTeamGranules;
       const bool has_dx = t < D - 1;
@@ -246,7 +234,7 @@ __global__ __launch_bounds__(kNT) void dec_bwd_persistent_kernel(DecBwdPersisten
       if (wid < 2) {
         if (has_dx && t + 1 < tile_last) {
           unsigned xv[1] = {0u};
-          sweep<1, kSleep>(tb + oGdx + (par ^ 1) * kGdx + j * kE, wid * 64, tag + 1u, xv, dead, a->err, 4u, lane);
+          sweep<1, kSleep>(tb + oGdx + (par ^ 1) * kGdx + j * kE, wid * 64, tag + 1u, xv, dead, a->err, kErrDecBwd, lane);
           dxv = __uint_as_float(xv[0]);
         }
         // lane l of the position loop uses features (l & 15) * 8 .. + 8 as four pairs
@@ -383,7 +371,7 @@ __global__ __launch_bounds__(kNT) void dec_bwd_persistent_kernel(DecBwdPersisten
       flush();
     }
     {  // P ds_t
-      KArgs* a = phase_args();
+      KArgs* a = phase_args<DecBwdPersistentArgs>();
       const int tid = phase_tid();
       if (tid < kA) {
         const float dn = __shfl_xor(ds_val, 1, 64);  // (waves 0-7, all lanes)
@@ -396,7 +384,7 @@ __global__ __launch_bounds__(kNT) void dec_bwd_persistent_kernel(DecBwdPersisten
     // ---- s-projection + cell backward of units [16j, 16j + 16)
     unsigned dz0 = 0u, dz1 = 0u;
     {
-      KArgs* a = phase_args();
+      KArgs* a = phase_args<DecBwdPersistentArgs>();
       const int tid = phase_tid(), wid = tid >> 6, lane = tid & 63;
       const int l15 = lane & 15, kof = 8 * (lane >> 4);
       const int row = (lane >> 4) * 4 + (wid & 3), u = 16 * j + l15;  // this thread's (row, unit), waves 0-3
@@ -416,7 +404,7 @@ __global__ __launch_bounds__(kNT) void dec_bwd_persistent_kernel(DecBwdPersisten
       }
       {  // W ds_t: wave wid takes row wid (256 bf16 pairs)
         unsigned dv[4] = {0u, 0u, 0u, 0u};
-        sweep<4, kSleep>(tb + oGds + par * kGds, wid * (kA / 2), tag, dv, dead, a->err, 4u, lane);
+        sweep<4, kSleep>(tb + oGds + par * kGds, wid * (kA / 2), tag, dv, dead, a->err, kErrDecBwd, lane);
 #pragma unroll
         for (int q = 0; q < 4; ++q) *reinterpret_cast<unsigned*>(dsl + wid * kWsS + 2 * (q * 64 + lane)) = dv[q];
       }
@@ -469,7 +457,7 @@ __global__ __launch_bounds__(kNT) void dec_bwd_persistent_kernel(DecBwdPersisten
     // ---- dh tile and (j < 8) dx tile of dz_t . W_cell^T
     float dxo = 0.f;
     {
-      KArgs* a = phase_args();
+      KArgs* a = phase_args<DecBwdPersistentArgs>();
       const int tid = phase_tid(), wid = tid >> 6, lane = tid & 63;
       const int l15 = lane & 15, kof = 8 * (lane >> 4);
       const int w = wid & 3, row = (lane >> 4) * 4 + w;
@@ -479,7 +467,7 @@ __global__ __launch_bounds__(kNT) void dec_bwd_persistent_kernel(DecBwdPersisten
       if (dxw && a->dX_dir) dxd = a->dX_dir[((size_t)t * B + r0 + row) * kE + 16 * j + l15];
       {  // W dz_t: wave wid takes row wid (2 gate pairs x 256 units)
         unsigned zv[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-        sweep<8, kSleep>(tb + oGdz + par * kGdz, wid * (2 * kH), tag, zv, dead, a->err, 4u, lane);
+        sweep<8, kSleep>(tb + oGdz + par * kGdz, wid * (2 * kH), tag, zv, dead, a->err, kErrDecBwd, lane);
         unsigned short* zr = reinterpret_cast<unsigned short*>(dzl + wid * kWzS);
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
@@ -521,7 +509,7 @@ __global__ __launch_bounds__(kNT) void dec_bwd_persistent_kernel(DecBwdPersisten
   }
   flush();
   {
-    KArgs* a = phase_args();
+    KArgs* a = phase_args<DecBwdPersistentArgs>();
     const int tid = phase_tid(), wid = tid >> 6, lane = tid & 63;
     if (wid < 4) {
       const size_t ri = (size_t)(r0 + (lane >> 4) * 4 + wid) * kH + 16 * j + (lane & 15);
@@ -535,23 +523,10 @@ __global__ __launch_bounds__(kNT) void dec_bwd_persistent_kernel(DecBwdPersisten
 // (shape rule and grid: dec_persistent_shape_ok / dec_persistent_grid of decoder_persistent.hip)
 size_t dec_bwd_persistent_xbuf_elems(int B) { return (size_t)(B / 16) * kTeamGranules; }
 
-// workgroups the current device keeps resident at once (one per CU when the occupancy query admits
-// the kernel with its LDS; 0 when it does not or there is no device); see dec_persistent_capacity
+// resident workgroups on the current device (handoff.h)
 int dec_bwd_persistent_capacity() {
-  static std::mutex mu;
-  static int cache[64] = {};  // [device] -> capacity + 1 (guarded by mu)
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-  std::lock_guard<std::mutex> lock(mu);
-  if (cache[dev]) return cache[dev] - 1;
-  int cus = 0, occ = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
-  bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(dec_bwd_persistent_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLds) == hipSuccess;
-  ok = ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, dec_bwd_persistent_kernel, kNT, kLds) == hipSuccess;
-  const int cap = (ok && occ >= 1) ? cus : 0;
-  cache[dev] = cap + 1;
-  return cap;
+  static int cache[kMaxDevices] = {};
+  return resident_capacity(cache, {{reinterpret_cast<const void*>(dec_bwd_persistent_kernel), kNT, kLds}});
 }
 
 void launch_dec_bwd_persistent(const bf16* G, const bf16* F, const float* S, const float* v, const float* wc,

@@ -11,7 +11,7 @@
 //   * three hand-offs per step stay inside the team (handoff.h: tagged 8-byte granules, members on
 //     one XCD): g_{t-1} (16 x 128 bf16) into the cell, [c_t, h_t] (16 x 512 bf16) into the
 //     s-projection, s_t (fp32, each workgroup reads its own row) into the attention;
-//   * every wait is bounded (sweep): a timeout records code 3 in *err and the grid drains.
+//   * every wait is bounded (sweep): a timeout records kErrDecFwd in *err and the grid drains.
 // Order of a step in one workgroup (P = publish, W = sweep, st = plain global stores):
 //   W g_{t-1} | cell | P [c,h]_t | W [c,h]_t | s-projection | P s_t | W s_t (own row) |
 //   first F / G loads | st Cst Cb Hb ACT S | position loop | P g_t | st ATT ATTb COV covloss
@@ -47,7 +47,6 @@
 #include "attn_rowp_fwd.h"
 #include "handoff.h"
 #include "launchers.h"
-#include <mutex>
 
 using namespace attn_rowp;
 using namespace handoff;
@@ -114,21 +113,7 @@ struct DecPersistentArgs {
 
 namespace {
 
-// The kernel's arguments, read from the kernarg segment where they are used.  The segment pointer is
-// made opaque once per phase: a phase loads the few pointers it needs into SGPRs and drops them at
-// its end, instead of all 24 staying live (and spilling) through the whole step loop.
-typedef const DecPersistentArgs __attribute__((address_space(4))) KArgs;
-__device__ __forceinline__ KArgs* phase_args() {
-  KArgs* a = (KArgs*)__builtin_amdgcn_kernarg_segment_ptr();  // the struct is the only argument
-  asm volatile("" : "+s"(a));
-  return a;
-}
-// The thread index, opaque per phase, so that a phase's per-thread addresses are re-derived in it.
-__device__ __forceinline__ int phase_tid() {
-  int t = threadIdx.x;
-  asm volatile("" : "+v"(t));
-  return t;
-}
+typedef const DecPersistentArgs __attribute__((address_space(4))) KArgs;  // see phase_args (handoff.h)
 
 // Src of the attention body (attn_rowp_fwd.h): the LDS-resident copies.
 struct ResidentSrc {
@@ -234,14 +219,14 @@ __global__ __launch_bounds__(kNT) void dec_fwd_persistent_kernel(DecPersistentAr
     float dc = 0.f, dh = 0.f, dgate[4] = {0.f, 0.f, 0.f, 0.f}, ds = 0.f;
     // ---- cell: z = XG_t + [g_{t-1}, h_{t-1}] . Wc^T
     {
-      KArgs* a = phase_args();
+      KArgs* a = phase_args<DecPersistentArgs>();
       const int tid = phase_tid(), wid = tid >> 6, lane = tid & 63;
       const int l15 = lane & 15, kof = 8 * (lane >> 4);
       const int crow = (lane >> 4) * 4 + (wid & 3), cu = 16 * j + l15;  // (the accumulator register wid of the MFMA tile)
       gu64* gbuf = a->xbuf + (size_t)team * kTeamGranules;
       if (t > 0) {  // g_{t-1}: wave wid takes row wid (64 bf16 pairs)
         unsigned gv[1] = {0u};
-        sweep<1, kSleep>(gbuf + (par ^ 1) * kGg, wid * 64, tag - 1u, gv, dead, a->err, 3u, lane);
+        sweep<1, kSleep>(gbuf + (par ^ 1) * kGg, wid * 64, tag - 1u, gv, dead, a->err, kErrDecFwd, lane);
         *reinterpret_cast<unsigned*>(gt + wid * kGtS + 2 * lane) = gv[0];
       }
       DEC_STAMP(0);
@@ -292,7 +277,7 @@ __global__ __launch_bounds__(kNT) void dec_fwd_persistent_kernel(DecPersistentAr
       DEC_STAMP(1);
       // ---- [c_t, h_t] of the tile: wave wid takes row wid (256 {c, h} granules)
       unsigned cv[4] = {0u, 0u, 0u, 0u};
-      sweep<4, kSleep>(chbuf + par * kGch, wid * kH, tag, cv, dead, a->err, 3u, lane);
+      sweep<4, kSleep>(chbuf + par * kGch, wid * kH, tag, cv, dead, a->err, kErrDecFwd, lane);
       unsigned short* crw = reinterpret_cast<unsigned short*>(ch + wid * kChS);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -304,7 +289,7 @@ __global__ __launch_bounds__(kNT) void dec_fwd_persistent_kernel(DecPersistentAr
     __syncthreads();
     // ---- s-projection: s = [c, h] . Ws^T + b, two 16-column tiles, linear2's four K slices
     {
-      KArgs* a = phase_args();
+      KArgs* a = phase_args<DecPersistentArgs>();
       const int tid = phase_tid(), wid = tid >> 6, lane = tid & 63;
       const int l15 = lane & 15, kof = 8 * (lane >> 4);
       const int w = wid & 3, nt2 = (wid >> 2) & 1;
@@ -334,7 +319,7 @@ __global__ __launch_bounds__(kNT) void dec_fwd_persistent_kernel(DecPersistentAr
     }
     // ---- attention of row j
     {
-      KArgs* a = phase_args();
+      KArgs* a = phase_args<DecPersistentArgs>();
       const bf16 *Fp = a->F, *Gp = a->G;
       const int* lens = a->lens;
       const int* dlen = a->dlen;
@@ -345,7 +330,7 @@ __global__ __launch_bounds__(kNT) void dec_fwd_persistent_kernel(DecPersistentAr
         const int tid = phase_tid(), wid = tid >> 6, lane = tid & 63;
         if (t < row_last && wid < 8) {
           unsigned sv[1] = {0u};
-          sweep<1, kSleep>(gbuf + 2 * kGg + 2 * kGch + par * kGs + j * kA, wid * 64, tag, sv, dead, a->err, 3u, lane);
+          sweep<1, kSleep>(gbuf + 2 * kGg + 2 * kGch + par * kGs + j * kA, wid * 64, tag, sv, dead, a->err, kErrDecFwd, lane);
           srow[wid * 64 + lane] = __uint_as_float(sv[0]);
         }
       }
@@ -363,7 +348,7 @@ __global__ __launch_bounds__(kNT) void dec_fwd_persistent_kernel(DecPersistentAr
                 if (!(k & 1)) store_granule(gdst + (k >> 1), tag, pack_bf2(g, gn));
               },
               [&]() {  // the cell's and the s-projection's stores of this step
-                KArgs* a2 = phase_args();
+                KArgs* a2 = phase_args<DecPersistentArgs>();
                 const int tid = phase_tid(), wid = tid >> 6, lane = tid & 63;
                 const int l15 = lane & 15, w = wid & 3, rw = (lane >> 4) * 4 + w;
                 if (wid < 4) {
@@ -399,7 +384,7 @@ __global__ __launch_bounds__(kNT) void dec_fwd_persistent_kernel(DecPersistentAr
   // ---- the tile's dead steps: the zeros dec_cell_fwd and attn_fwd_rowp write (coverage carried)
   __syncthreads();  // (the resident coverage written in the last live step by other threads)
   for (int t = tile_last; t < D; ++t) {
-    KArgs* a = phase_args();
+    KArgs* a = phase_args<DecPersistentArgs>();
     const int tid = phase_tid(), wid = tid >> 6, lane = tid & 63;
     if (wid < 4) {
       const int crow = (lane >> 4) * 4 + (wid & 3), cu = 16 * j + (lane & 15);
@@ -423,8 +408,8 @@ bool dec_persistent_shape_ok(int H, int E, int A, int B, int T) {
   return H == kH && E == kE && A == kA && B >= 16 && B % 16 == 0 && T >= 1 && T <= kRowMaxT;
 }
 
-// workgroups of a launch: teams are dealt 8 at a time (one per XCD), 16 members each
-int dec_persistent_grid(int B) { return B >= 16 && B % 16 == 0 ? 8 * kNC * ((B / 16 + 7) / 8) : 0; }
+// workgroups of a launch: one team of 16 per 16-row tile
+int dec_persistent_grid(int B) { return B >= 16 && B % 16 == 0 ? team_grid(kNC, B / 16) : 0; }
 
 size_t dec_persistent_xbuf_elems(int B) { return (size_t)(B / 16) * kTeamGranules; }
 
@@ -444,25 +429,10 @@ int dec_persistent_stamps_into(unsigned* buf) {
 #endif
 }
 
-// workgroups the current device keeps resident at once (one per CU when the occupancy query admits
-// the kernel with its LDS; 0 when it does not or there is no device).  The count assumes the launch
-// has every CU of the device to itself: see dec_persistent_eligible (models/engine_config.py) for
-// the invariant the engine keeps.
+// resident workgroups on the current device (handoff.h; the engine's invariant: dec_persistent_eligible)
 int dec_persistent_capacity() {
-  static std::mutex mu;
-  static int cache[64] = {};  // [device] -> capacity + 1 (guarded by mu)
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-  std::lock_guard<std::mutex> lock(mu);
-  if (cache[dev]) return cache[dev] - 1;
-  int cus = 0, occ = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
-  bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(dec_fwd_persistent_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLds) == hipSuccess;
-  ok = ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, dec_fwd_persistent_kernel, kNT, kLds) == hipSuccess;
-  const int cap = (ok && occ >= 1) ? cus : 0;
-  cache[dev] = cap + 1;
-  return cap;
+  static int cache[kMaxDevices] = {};
+  return resident_capacity(cache, {{reinterpret_cast<const void*>(dec_fwd_persistent_kernel), kNT, kLds}});
 }
 
 void launch_dec_fwd_persistent(const float* XG, const bf16* KcT, const bf16* WsT, const float* bs, float* Cst, bf16* Cb,

@@ -1,12 +1,15 @@
 // In-launch hand-offs between the workgroups of a persistent kernel (lstm_persistent.hip,
-// decoder_persistent.hip): the data is the flag.  A payload travels as 8-byte {tag, value}
-// granules, each written with ONE agent-scope store and polled with agent-scope loads until the
-// tag matches (tags = step index + 1; the granule buffer is zeroed before every launch).  Team
-// members are placed on one XCD (team_of), so a hand-off stays in that XCD's L2.  Every spin is
-// bounded: on timeout the wave records a code in *err and stops waiting (results are then
-// garbage, but the grid always drains).
+// decoder_persistent.hip, decoder_bwd_persistent.hip): the data is the flag.  A payload travels as
+// 8-byte {tag, value} granules, each written with ONE agent-scope store and polled with agent-scope
+// loads until the tag matches (tags = step index + 1; the granule buffer is zeroed before every
+// launch).  Team members are placed on one XCD (team_of), so a hand-off stays in that XCD's L2.
+// Every spin is bounded: on timeout the wave records its family's code (the enum below; messages:
+// HANDOFF_CODES in models/engine_config.py) in *err and stops waiting (results are then garbage,
+// but the grid always drains).  The host side is here too: team_grid and resident_capacity.
 #pragma once
 #include "common.h"
+#include <initializer_list>
+#include <mutex>
 
 #define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
@@ -16,6 +19,7 @@ typedef __attribute__((address_space(1))) unsigned long long gu64;
 typedef __attribute__((address_space(1))) unsigned int gu32;
 // a sweep gives up after kSpinLimit / 4 passes with s_sleep(SLEEP) between them: ~0.1-1 s at 24
 constexpr unsigned kSpinLimit = 1u << 21;
+enum : unsigned { kErrLstmFwd = 1, kErrLstmBwd = 2, kErrDecFwd = 3, kErrDecBwd = 4 };
 
 __device__ __forceinline__ unsigned pack_bf2(float lo, float hi) {
   const unsigned a = __builtin_bit_cast(unsigned short, f2bf(lo));
@@ -69,6 +73,58 @@ __device__ __forceinline__ bool team_of(int NC, int nteams, int& team, int& c) {
   team = (q / NC) * 8 + xcd;
   c = q % NC;
   return team < nteams;
+}
+
+// The kernel's arguments (one struct), read from the kernarg segment where they are used.  The segment
+// pointer is made opaque once per phase: a phase loads the few pointers it needs into SGPRs and drops
+// them at its end, instead of all of them staying live (and spilling) through the whole step loop.
+template <class Args>
+__device__ __forceinline__ const Args __attribute__((address_space(4)))* phase_args() {
+  typedef const Args __attribute__((address_space(4))) KArgs;
+  KArgs* a = (KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(a));
+  return a;
+}
+// The thread index, opaque per phase, so that a phase's per-thread addresses are re-derived in it.
+__device__ __forceinline__ int phase_tid() {
+  int t = threadIdx.x;
+  asm volatile("" : "+v"(t));
+  return t;
+}
+
+// ------------------------------------------------------------------------------ host side
+// workgroups of a launch: nteams teams of NC workgroups, dealt 8 at a time (one per XCD, see team_of)
+constexpr int team_grid(int NC, int nteams) { return 8 * NC * ((nteams + 7) / 8); }
+
+struct Probe {  // one kernel variant of a persistent family, as it is launched
+  const void* kernel;
+  int threads, dyn_lds;
+};
+constexpr int kMaxDevices = 64;
+// Workgroups the current device keeps resident at once: the CU count the runtime reports (not an
+// assumed 256: a partitioned or smaller device shrinks the admissible grid instead of spinning into
+// the timeout) when the occupancy query admits every probe, else 0, as without a device.  It also
+// sets MaxDynamicSharedMemorySize, so launchers call it first.  What may hold CUs beside the launch
+// comes off it in fits_resident (models/engine_config.py).  cache: one per probe list, capacity + 1.
+inline int resident_capacity(int (&cache)[kMaxDevices], std::initializer_list<Probe> probes) {
+  static std::mutex mu;  // guards every cache
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return 0;
+  std::lock_guard<std::mutex> lock(mu);
+  if (cache[dev]) return cache[dev] - 1;
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
+  bool ok = true;
+  for (const Probe& p : probes) {
+    int occ = 0;
+    if (p.dyn_lds > 0)
+      ok = ok && hipFuncSetAttribute(p.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, p.dyn_lds) == hipSuccess;
+    ok = ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, p.kernel, p.threads, p.dyn_lds) == hipSuccess &&
+         occ >= 1;
+  }
+  const int cap = ok ? cus : 0;
+  cache[dev] = cap + 1;
+  return cap;
 }
 
 }  // namespace handoff

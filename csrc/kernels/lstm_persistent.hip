@@ -265,7 +265,7 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_persistent_kernel(
       for (int ch = 0; ch < NPL / CH; ++ch) {
         unsigned v[CH];
         const int first = wid * (G / 4) + ch * CH * 64;
-        sweep<CH>(xb + (size_t)(s & 1) * G, first, (unsigned)s, v, dead, err, 1u, lane);
+        sweep<CH>(xb + (size_t)(s & 1) * G, first, (unsigned)s, v, dead, err, kErrLstmFwd, lane);
 #pragma unroll
         for (int j = 0; j < CH; ++j) {
           const int idx = first + j * 64 + lane;
@@ -476,7 +476,7 @@ __global__ __launch_bounds__(512, 1) void lstm_fwd_persistent8_kernel(
       }
     } else {
       unsigned v[NPL];
-      sweep<NPL>(xb + (size_t)(s & 1) * G, wid * (G / 8), (unsigned)s, v, dead, err, 1u, lane);
+      sweep<NPL>(xb + (size_t)(s & 1) * G, wid * (G / 8), (unsigned)s, v, dead, err, kErrLstmFwd, lane);
 #pragma unroll
       for (int j = 0; j < NPL; ++j) {
         const int idx = wid * (G / 8) + j * 64 + lane;
@@ -663,7 +663,7 @@ __global__ __launch_bounds__(64 * NW, 1) void lstm_bwd_persistent_kernel(
               }
             if (__all((ready & need) == need) || dead) break;
             if (++spins > kSpinLimit / 4) {
-              if (lane == 0) __hip_atomic_store(err, 2u, RLX_AGENT);
+              if (lane == 0) __hip_atomic_store(err, kErrLstmBwd, RLX_AGENT);
               dead = true;
               break;
             }
@@ -925,7 +925,7 @@ __global__ __launch_bounds__(1024, 1) void lstm_bwd_persistent32_kernel(
             }
           if (__all((ready & need) == need) || dead) break;
           if (++spins > kSpinLimit / 4) {
-            if (lane == 0) __hip_atomic_store(err, 2u, RLX_AGENT);
+            if (lane == 0) __hip_atomic_store(err, kErrLstmBwd, RLX_AGENT);
             dead = true;
             break;
           }
@@ -1050,45 +1050,29 @@ static int lstm_nw(int H) { return H == 512 ? 8 : 4; }  // forward waves per wor
 
 static bool lstm_h_ok(int H) { return H == 64 || H == 128 || H == 256 || H == 512; }
 
-// Workgroups of the persistent kernels the current device keeps resident at once: one per
-// CU (launch bounds (64 NW, 1); the occupancy query must admit at least that for every
-// variant), times the CU count the runtime reports -- not an assumed 256, so a partitioned
-// or smaller device shrinks the admissible grid instead of spinning into the hand-off timeout.
+// resident workgroups on the current device (handoff.h): every variant launched at H must be admitted
+#define KERNEL(...) reinterpret_cast<const void*>(&__VA_ARGS__)
+template <int H>  // H <= 256: the BPTT, the 8-wave forward, the 4-wave forward without and with FX
+static int lstm_capacity_h() {
+  static int cache[kMaxDevices] = {};
+  return resident_capacity(cache, {{KERNEL(lstm_bwd_persistent_kernel<H, 8, false>), 512, 0},
+                                   {KERNEL(lstm_fwd_persistent8_kernel<H, true>), 512, 0},
+                                   {KERNEL(lstm_fwd_persistent_kernel<H, true>), 256, 0},
+                                   {KERNEL(lstm_fwd_persistent_kernel<H, true, 1, true>), 256, 0}});
+}
+template <>  // H = 512: its 4-wave forward is the 32-row one, and the 32-row BPTT comes with it
+int lstm_capacity_h<512>() {
+  static int cache[kMaxDevices] = {};
+  return resident_capacity(cache, {{KERNEL(lstm_bwd_persistent_kernel<512, 8, false>), 512, 0},
+                                   {KERNEL(lstm_fwd_persistent8_kernel<512, true>), 512, 0},
+                                   {KERNEL(lstm_fwd_persistent_kernel<512, true, 2>), 256, 0},
+                                   {KERNEL(lstm_fwd_persistent_kernel<512, true, 2, true>), 256, 0},
+                                   {KERNEL(lstm_bwd_persistent32_kernel<false>), 1024, 0}});
+}
+#undef KERNEL
 int lstm_persistent_capacity(int H) {
-  static int cache[64][4] = {};  // [device][log2(H/64)] -> capacity + 1
-  int dev = 0;
-  if (!lstm_h_ok(H) || hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-  const int hi = H == 64 ? 0 : H == 128 ? 1 : H == 256 ? 2 : 3;
-  if (cache[dev][hi]) return cache[dev][hi] - 1;
-  int cus = 0, o[4] = {1, 1, 1, 1};
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
-  bool ok = true;
-#define OCC(HH)                                                                                                    \
-  if (H == HH) {                                                                                                   \
-    ok &= hipOccupancyMaxActiveBlocksPerMultiprocessor(&o[0], lstm_bwd_persistent_kernel<HH, 8, false>, 512, 0) == hipSuccess; \
-    ok &= hipOccupancyMaxActiveBlocksPerMultiprocessor(&o[1], lstm_fwd_persistent8_kernel<HH, true>, 512, 0) == hipSuccess; \
-    if (HH <= 256) {                                                                                               \
-      ok &= hipOccupancyMaxActiveBlocksPerMultiprocessor(&o[3], lstm_fwd_persistent_kernel<(HH <= 256 ? HH : 256), true>, \
-                                                         256, 0) == hipSuccess;                                    \
-      int ofx = 0;                                                                                                 \
-      ok &= hipOccupancyMaxActiveBlocksPerMultiprocessor(                                                          \
-                &ofx, lstm_fwd_persistent_kernel<(HH <= 256 ? HH : 256), true, 1, true>, 256, 0) == hipSuccess;    \
-      o[3] = min(o[3], ofx);                                                                                       \
-    } else {                                                                                                       \
-      ok &= hipOccupancyMaxActiveBlocksPerMultiprocessor(&o[2], lstm_fwd_persistent_kernel<512, true, 2>, 256, 0) == hipSuccess; \
-      int ofx = 0;                                                                                                 \
-      ok &= hipOccupancyMaxActiveBlocksPerMultiprocessor(&ofx, lstm_fwd_persistent_kernel<512, true, 2, true>, 256, 0) == hipSuccess; \
-      o[2] = min(o[2], ofx);                                                                                       \
-      int o32 = 0;                                                                                                 \
-      ok &= hipOccupancyMaxActiveBlocksPerMultiprocessor(&o32, lstm_bwd_persistent32_kernel<false>, 1024, 0) == hipSuccess; \
-      o[2] = min(o[2], o32);                                                                                      \
-    }                                                                                                              \
-  }
-  OCC(64) OCC(128) OCC(256) OCC(512)
-#undef OCC
-  const int cap = (ok && o[0] >= 1 && o[1] >= 1 && o[2] >= 1 && o[3] >= 1) ? cus : 0;
-  cache[dev][hi] = cap + 1;
-  return cap;
+  return H == 64 ? lstm_capacity_h<64>() : H == 128 ? lstm_capacity_h<128>() : H == 256 ? lstm_capacity_h<256>()
+       : H == 512 ? lstm_capacity_h<512>() : 0;
 }
 
 // Rows per team: 16, or 32 for the H = 512 forward above batch 256 (the 4-wave RT = 2 kernel:
@@ -1116,7 +1100,7 @@ static int lstm_rows(int H, int B, bool bwd) {
 static int lstm_tiles_per_launch(int H, int ntile) {
   const int NC = H / 64, cap = lstm_persistent_capacity(H);
   int nl = ntile;
-  while (nl > 0 && 8 * NC * ((2 * nl + 7) / 8) > cap) --nl;
+  while (nl > 0 && team_grid(NC, 2 * nl) > cap) --nl;
   return nl;
 }
 
@@ -1126,7 +1110,7 @@ int lstm_persistent_grid(int H, int B) {
   for (int bwd = 0; bwd < 2; ++bwd) {
     const int R = lstm_rows(H, B, bwd), NC = H / 64, nl = lstm_tiles_per_launch(H, (B + R - 1) / R);
     if (nl <= 0) return 0;
-    grid = max(grid, 8 * NC * ((2 * nl + 7) / 8));  // grid of the largest launch
+    grid = max(grid, team_grid(NC, 2 * nl));  // grid of the largest launch
   }
   return grid;
 }
@@ -1164,7 +1148,7 @@ void launch_lstm_fwd_persistent(const float* gx, const float* bias, const bf16* 
   gu64* xb = (gu64*)xbuf;
   gu32* e = (gu32*)err;
   for (int t0 = 0; t0 < ntile; t0 += nl) {
-    const int n = min(nl, ntile - t0), grid = 8 * NC * ((2 * n + 7) / 8);
+    const int n = min(nl, ntile - t0), grid = team_grid(NC, 2 * n);
 #define ARGS gx, bias, Wt, hs, cs, acts, out, lens, xb, e, T, B, ntile, t0, n, xsf, Wx0, Wx1
 #define LAUNCH_F(HH, NTV)                                                                                            \
   if (fx && R == 32)                                                                                            \
@@ -1197,7 +1181,7 @@ void launch_lstm_bwd_persistent(bf16* dz, const bf16* Wn, const float* dout, con
   gu64* xb = (gu64*)xbuf;
   gu32* e = (gu32*)err;
   for (int t0 = 0; t0 < ntile; t0 += nl) {
-    const int n = min(nl, ntile - t0), grid = 8 * NC * ((2 * n + 7) / 8);
+    const int n = min(nl, ntile - t0), grid = team_grid(NC, 2 * n);
     if (R == 32) {
 #define LB32(PC, SL, DB, STP) hipLaunchKernelGGL((lstm_bwd_persistent32_kernel<false, PC, SL, DB, STP>), dim3(grid), \
                                                  dim3(1024), 0, st, dz, Wn, dout, dh_fin, dc_carry, acts, cs, lens, xb, e, \

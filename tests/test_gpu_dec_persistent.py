@@ -250,10 +250,17 @@ def test_dec_fwd_persistent_graph_replay():
 def test_dec_persistent_grid_matches_engine_config():
     """The engine decides with engine_config.dec_persistent_grid and the binding checks the
     library's: the two must agree, or an eligible shape would raise instead of falling back."""
-    from textsummarization_on_flink_amd.models.engine_config import dec_persistent_grid
+    from textsummarization_on_flink_amd.models.engine_config import dec_persistent_eligible, dec_persistent_grid
     k = _k()
     for B in (0, 8, 16, 24, 48, 128, 144, 250, 256, 272, 1024):
         assert int(k.dec_persistent_grid(B)) == dec_persistent_grid(B), B
+    # the shape rule likewise (ample capacity on the Python side, so only the shape decides)
+    for H, E, A in ((256, 128, 512), (512, 128, 1024), (256, 64, 512)):
+        for B in (8, 16, 24, 32, 256, 272):
+            for T in (0, 1, 2048, 2049):
+                py = dec_persistent_eligible(H=H, E=E, A=A, B=B, T=T, proj_attn=True, row_attn=True, world=1,
+                                             capacity=1 << 20, reserve_cus=0)
+                assert bool(k.dec_persistent_ok(H, E, A, B, T)) == py, (H, E, A, B, T)
 
 
 def test_dec_persistent_eligibility():

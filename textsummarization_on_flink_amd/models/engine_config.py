@@ -27,7 +27,7 @@ from __future__ import annotations
 
 import os
 from dataclasses import dataclass, fields, replace
-from typing import Mapping, Optional
+from typing import Dict, Mapping, Optional, Tuple
 
 
 def _flag(env: Mapping[str, str], name: str, default: bool) -> bool:
@@ -82,7 +82,36 @@ class EngineConfig:
         return {f.name: getattr(self, f.name) for f in fields(self)}
 
 
-DEC_PERSISTENT_TEAM = 16  # workgroups per 16-row tile (csrc/kernels/decoder_persistent.hip)
+# team scheme and shape rule of csrc/kernels/decoder_persistent.hip (tests/test_gpu_dec_persistent.py compares them)
+DEC_PERSISTENT_TEAM = 16  # workgroups per 16-row tile
+DEC_PERSISTENT_SHAPE = (256, 128, 512)  # (H, E, A)
+DEC_PERSISTENT_MAX_T = 2048
+
+# hand-off timeout codes (csrc/kernels/handoff.h, kErr*) -> (the kernel, its env switch, its EngineConfig field)
+HANDOFF_CODES: Dict[int, Tuple[str, str, str]] = {
+    1: ("persistent LSTM", "TSAMD_LSTM_PERSISTENT", "persistent_lstm"),
+    2: ("persistent LSTM", "TSAMD_LSTM_PERSISTENT", "persistent_lstm"),
+    3: ("persistent decoder forward", "TSAMD_DEC_PERSISTENT", "dec_persistent"),
+    4: ("persistent decoder backward", "TSAMD_DEC_BWD_PERSISTENT", "dec_bwd_persistent"),
+}
+
+
+def handoff_error_message(code: int) -> Optional[str]:
+    """The message for a hand-off error word: None for 0 (no timeout)."""
+    if not code:
+        return None
+    if code not in HANDOFF_CODES:
+        return f"a persistent kernel's hand-off timed out (unknown code {code}); results of that launch were discarded"
+    what, env, field = HANDOFF_CODES[code]
+    return (f"{what} hand-off timed out (code {code}: a workgroup was not co-resident); results of that launch "
+            f"were discarded -- set {env}=0 (EngineConfig.{field})")
+
+
+def fits_resident(grid: int, capacity: int, world: int, reserve_cus: int) -> bool:
+    """Whether a grid whose workgroups wait for each other is co-resident: it fits ``capacity`` (the
+    occupancy query's resident workgroup count, 0 without a device), less ``reserve_cus`` (the CUs
+    an in-flight RCCL collective may hold) when there is more than one rank."""
+    return 0 < grid <= capacity - (reserve_cus if world > 1 else 0)
 
 
 def dec_persistent_grid(B: int) -> int:
@@ -98,9 +127,7 @@ def dec_persistent_eligible(H: int, E: int, A: int, B: int, T: int, proj_attn: b
     shape, the attention path, the world size and the device's resident capacity).
 
     The kernel covers the headline family only (hidden 256, emb 128, A = 512, projected row
-    attention, whole 16-row tiles) and its workgroups wait for each other, so the whole grid must
-    be co-resident: ``capacity`` is the occupancy query's resident workgroup count, and with more
-    than one rank ``reserve_cus`` (the CUs an in-flight RCCL collective may hold) comes off it.
+    attention, whole 16-row tiles) and its workgroups wait for each other (``fits_resident``).
     Not eligible means the three-kernel chains, never an error.
 
     Invariant behind ``capacity``: it is one workgroup per CU of the whole device, and at the
@@ -112,11 +139,9 @@ def dec_persistent_eligible(H: int, E: int, A: int, B: int, T: int, proj_attn: b
     RCCL's CUs do, or workgroups wait for unscheduled peers until the hand-off timeout."""
     if not (proj_attn and row_attn):
         return False
-    if (H, E, A) != (256, 128, 512) or B < 16 or B % 16 or not 1 <= T <= 2048:
+    if (H, E, A) != DEC_PERSISTENT_SHAPE or not 1 <= T <= DEC_PERSISTENT_MAX_T:
         return False
-    grid = dec_persistent_grid(B)
-    cap = capacity - (reserve_cus if world > 1 else 0)
-    return 0 < grid <= cap
+    return fits_resident(dec_persistent_grid(B), capacity, world, reserve_cus)  # (grid 0: B is not whole tiles)
 
 
 def dec_bwd_persistent_eligible(H: int, E: int, A: int, B: int, T: int, proj_attn: bool, row_attn: bool,

@@ -30,7 +30,7 @@ import torch
 
 from ..ops import ops as _ops
 from ..parallel.rccl_env import rccl_cu_reserve
-from .engine_config import EngineConfig, dec_bwd_persistent_eligible, dec_persistent_eligible
+from .engine_config import EngineConfig, dec_bwd_persistent_eligible, dec_persistent_eligible, handoff_error_message
 from .params import DEC, P, FlatParams, enc_prefix
 
 BF = torch.bfloat16
@@ -461,6 +461,9 @@ class HipPointerGenerator:
         # set by a data-parallel trainer: a persistent-LSTM timeout poisons the last gradient
         # element before its bucket's all-reduce, so every rank skips that update (poison_where)
         self.poison_on_lstm_err = False
+        self.split_vocab_dw = False  # see _dw_job (the graph trainer sets it with TSAMD_VOCAB_DW_SIDE)
+        self.dec_force_chains = set()  # "fwd" / "bwd": run that loop as chains although it is eligible (tools)
+        self._dec_xbuf = self._dec_bwd_xbuf = None
         self.nchunk = int(self.k.attn_chunks(T))
         # The decoder recurrences (forward: cell -> s-projection -> score -> softmax/context;
         # backward: attention step -> cell backward -> dz backward) are independent across
@@ -685,7 +688,6 @@ class HipPointerGenerator:
         w["DCTXb"] = z(D, B, A, dt=BF)
         self.de_bf16 = DE_BF16 and self.ctx_native and self.persistent_lstm
         self._dE = z(B, T, A, dt=BF if self.de_bf16 else F32)
-        self.split_vocab_dw = False  # see _dw_job (the graph trainer sets it with TSAMD_VOCAB_DW_SIDE)
         self._pending_dw = None
         # attn_bwd_feat partial rows (spread the atomics), summed after; deterministic mode: one
         # row per workgroup (a single writer per slot)
@@ -704,30 +706,32 @@ class HipPointerGenerator:
         self.w = w
 
     def _dec_persistent_select(self) -> None:
-        k = self.k
-        cap = int(k.dec_persistent_capacity()) if (self.cfg.dec_persistent and self.proj_attn) else 0
-        self.dec_persistent = self.cfg.dec_persistent and dec_persistent_eligible(
-            self.H, self.E, self.A, self.B, self.T, self.proj_attn, self.row_attn, self.world, cap,
-            rccl_cu_reserve())
-        if self.dec_persistent and getattr(self, "_dec_xbuf", None) is None:
-            self._dec_xbuf = torch.zeros(int(k.dec_persistent_xbuf(self.B)), dtype=torch.long, device=self.dev)
-        # the backward loop likewise (decoder_bwd_persistent.hip); the vocab-dW side stream is known only
-        # when the trainer has set split_vocab_dw, so dec_bwd_persistent_on() decides at call time
+        """Resident capacities of the two persistent decoder kernels and their hand-off buffers.  A buffer
+        exists whenever the device admits the kernel and the batch is whole tiles, i.e. for every world size /
+        side-stream setting dec_*_persistent_on() may later see (never at a call site: a capture may be on)."""
+        k, tiles = self.k, self.B >= 16 and self.B % 16 == 0
+        self._dec_cap = int(k.dec_persistent_capacity()) if (self.cfg.dec_persistent and self.proj_attn) else 0
         self._dec_bwd_cap = int(k.dec_bwd_persistent_capacity()) if (self.cfg.dec_bwd_persistent and self.proj_attn) else 0
-        # the hand-off buffer exists whenever the device admits the kernel and the batch is whole tiles, i.e.
-        # for every world size / side-stream setting that dec_bwd_persistent_on() may later see (it is
-        # not allocated at the call site: that may be inside a graph capture)
-        if self._dec_bwd_cap > 0 and self.B >= 16 and self.B % 16 == 0 and getattr(self, "_dec_bwd_xbuf", None) is None:
+        if self._dec_cap > 0 and tiles and self._dec_xbuf is None:
+            self._dec_xbuf = torch.zeros(int(k.dec_persistent_xbuf(self.B)), dtype=torch.long, device=self.dev)
+        if self._dec_bwd_cap > 0 and tiles and self._dec_bwd_xbuf is None:
             self._dec_bwd_xbuf = torch.zeros(int(k.dec_bwd_persistent_xbuf(self.B)), dtype=torch.long, device=self.dev)
 
-    # tools/phase_micro.py sets this to time backward_mid with the chains on an engine that is eligible
-    dec_bwd_force_chains = False
+    def _dec_shape(self):
+        return self.H, self.E, self.A, self.B, self.T, self.proj_attn, self.row_attn, self.world
+
+    def dec_fwd_persistent_on(self) -> bool:
+        """Whether _decoder_forward_proj runs the loop as the one persistent launch."""
+        return self.cfg.dec_persistent and "fwd" not in self.dec_force_chains and dec_persistent_eligible(
+            *self._dec_shape(), self._dec_cap, rccl_cu_reserve())
 
     def dec_bwd_persistent_on(self) -> bool:
-        """Whether _backward_mid_proj runs the reverse loop as the one persistent launch."""
-        return self.cfg.dec_bwd_persistent and not self.dec_bwd_force_chains and dec_bwd_persistent_eligible(
-            self.H, self.E, self.A, self.B, self.T, self.proj_attn, self.row_attn, self.world, self._dec_bwd_cap,
-            rccl_cu_reserve(), dw_side=bool(getattr(self, "split_vocab_dw", False)))
+        """Whether _backward_mid_proj runs the reverse loop as the one persistent launch (the vocab-dW
+        side stream is known only once the trainer has set split_vocab_dw, hence at call time)."""
+        return self.cfg.dec_bwd_persistent and "bwd" not in self.dec_force_chains and dec_bwd_persistent_eligible(
+            *self._dec_shape(), self._dec_bwd_cap, rccl_cu_reserve(), dw_side=bool(self.split_vocab_dw))
+
+    dec_persistent = property(dec_fwd_persistent_on)
 
     def set_world(self, world: int) -> None:
         """Data-parallel trainers: RCCL collectives of ``world`` > 1 ranks may hold CUs, which come
@@ -740,19 +744,9 @@ class HipPointerGenerator:
         engine was built: the persistent LSTM (codes 1 forward, 2 BPTT) or the persistent decoder
         forward / backward loop (codes 3 / 4), which share the word.  It is sticky: those results were garbage, the
         optimizer kernel skipped the update, and eval / decode must not report them."""
-        code = int(self.w["lstm_err"].item())
-        if code == 3:
-            raise LstmHandoffError("persistent decoder forward hand-off timed out (code 3: a workgroup was not "
-                                   "co-resident); results of that launch were discarded -- set "
-                                   "TSAMD_DEC_PERSISTENT=0 (EngineConfig.dec_persistent)")
-        if code == 4:
-            raise LstmHandoffError("persistent decoder backward hand-off timed out (code 4: a workgroup was not "
-                                   "co-resident); results of that launch were discarded -- set "
-                                   "TSAMD_DEC_BWD_PERSISTENT=0 (EngineConfig.dec_bwd_persistent)")
-        if code:
-            raise LstmHandoffError(f"persistent LSTM hand-off timed out (code {code}: a workgroup was not "
-                                   "co-resident); results of that launch were discarded -- set "
-                                   "TSAMD_LSTM_PERSISTENT=0 (EngineConfig.persistent_lstm)")
+        msg = handoff_error_message(int(self.w["lstm_err"].item()))
+        if msg:
+            raise LstmHandoffError(msg)
 
     # ------------------------------------------------------------------ weights
     def pack(self):
@@ -1072,7 +1066,7 @@ class HipPointerGenerator:
         v, wc = self.f32["v"], self.f32["wc"]
         dlen = w["dlen"] if self.skip_pad else None
 
-        if self.dec_persistent:
+        if self.dec_fwd_persistent_on():
             self._dec_xbuf.zero_()  # hand-off tags must start at 0 every launch
             k.dec_fwd_persistent(w["XG"], self.pk["KcT"], self.pk["WsT"], self.p[ATT_B], w["Cst"], w["Cb"], w["Hb"],
                                  w["ACT"], w["S"], F, G, v, wc, w["COV"] if cov else None, lens, w["ATT"], w["ATTb"],

@@ -31,6 +31,7 @@ from typing import Callable, Dict, Optional
 
 import torch
 
+from ..models.engine_config import fits_resident
 from ..models.params import FlatParams, build_params
 from ..models.pointer_generator import VOCAB_DW_SIDE, HipPointerGenerator, LstmHandoffError  # noqa: F401
 from ..parallel.dist import DistInfo, GradAllReducer, broadcast_params, rccl_cu_reserve
@@ -114,7 +115,8 @@ class GraphTrainer:
         if self.info.enabled and eng.persistent_lstm:
             grid = int(eng.k.lstm_persistent_grid(eng.H, eng.B))
             cap = int(eng.k.lstm_persistent_capacity(eng.H))
-            self.lstm_exclusive = grid > cap - max(LSTM_RCCL_RESERVE_CUS, rccl_cu_reserve())
+            reserve = max(LSTM_RCCL_RESERVE_CUS, rccl_cu_reserve())
+            self.lstm_exclusive = not fits_resident(grid, cap, self.info.world, reserve)
         self.use_graph = use_graph
         self.g_fb = None
         self.g_opt = None

@@ -13,7 +13,7 @@ decoder phase timed the same way right after it: both are enqueued while the GPU
 step, so neither contains the host's graph-launch time, which ``decoder_fwd`` (second phase after
 an idle GPU) can.  Likewise for the decoder backward loop (``dec_bwd_persistent``:
 TSAMD_DEC_BWD_PERSISTENT, eligible shape): ``backward_mid_chains`` is backward_mid with the switch
-off (``dec_bwd_force_chains`` on the engine) and ``backward_mid_queued`` the persistent one, each
+off (``dec_force_chains`` on the engine, as for the forward) and ``backward_mid_queued`` the persistent one, each
 timed behind a replay of backward_head.  These extra replays come after the step's optimizer phase,
 so they work on the updated weights and on gradient buffers the step has already consumed: the
 same shapes, lengths and dead steps, hence the same time, but their outputs mean nothing.
@@ -61,27 +61,21 @@ def main():
               ("optimizer", eng.optimizer_step)]
     nstep = len(phases)
 
-    def decoder_fwd_chains():
-        eng.dec_persistent = False
-        try:
-            eng._decoder_forward()
-        finally:
-            eng.dec_persistent = True
+    def chains(direction, fn):  # fn with that decoder loop as the per-step chains
+        def run():
+            eng.dec_force_chains.add(direction)
+            try:
+                fn()
+            finally:
+                eng.dec_force_chains.discard(direction)
+        return run
 
-    if eng.dec_persistent:
-        phases.append(("decoder_fwd_chains", decoder_fwd_chains))
-    bwd_persistent = bool(eng.dec_bwd_persistent_on())
-
-    def backward_mid_chains():
-        eng.dec_bwd_force_chains = True
-        try:
-            eng.backward_mid()
-        finally:
-            eng.dec_bwd_force_chains = False
-
+    fwd_persistent, bwd_persistent = bool(eng.dec_fwd_persistent_on()), bool(eng.dec_bwd_persistent_on())
+    if fwd_persistent:
+        phases.append(("decoder_fwd_chains", chains("fwd", eng._decoder_forward)))
     n_bwd = len(phases)  # index of backward_mid_chains when present
     if bwd_persistent:
-        phases.append(("backward_mid_chains", backward_mid_chains))
+        phases.append(("backward_mid_chains", chains("bwd", eng.backward_mid)))
     graphs = []
     pool = torch.cuda.graph_pool_handle()
     s = torch.cuda.Stream()
@@ -100,7 +94,7 @@ def main():
             graphs.append(g)
     torch.cuda.synchronize()
     res = {"batch": a.batch, "hidden": a.hidden, "enc": a.enc, "layers": a.layers,
-           "dec_persistent": bool(eng.dec_persistent), "dec_bwd_persistent": bwd_persistent}
+           "dec_persistent": fwd_persistent, "dec_bwd_persistent": bwd_persistent}
     ev_b = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
     tot_b = [0.0, 0.0]
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(phases) + 1)]
@@ -121,7 +115,7 @@ def main():
             ev_b[2].record()
             graphs[4].replay()
             ev_b[3].record()
-        if eng.dec_persistent:  # the chains right after an encoder forward, as the persistent launch above
+        if fwd_persistent:  # the chains right after an encoder forward, as the persistent launch above
             graphs[0].replay()
             ev_x.record()
             graphs[nstep].replay()
@@ -133,15 +127,15 @@ def main():
         torch.cuda.synchronize()
         for i in range(nstep):
             tot[i] += ev[i].elapsed_time(ev[i + 1])
-        if eng.dec_persistent:
+        if fwd_persistent:
             tot[nstep] += ev_x.elapsed_time(ev[nstep + 1])
             tot_y += ev_y[0].elapsed_time(ev_y[1])
         if bwd_persistent:
             tot_b[0] += ev_b[0].elapsed_time(ev_b[1])
             tot_b[1] += ev_b[2].elapsed_time(ev_b[3])
-    for (n, _), t in zip(phases[:nstep + (1 if eng.dec_persistent else 0)], tot):
+    for (n, _), t in zip(phases[:nstep + (1 if fwd_persistent else 0)], tot):
         res[n] = round(t / a.iters, 3)
-    if eng.dec_persistent:
+    if fwd_persistent:
         res["decoder_fwd_queued"] = round(tot_y / a.iters, 3)
     if bwd_persistent:
         res["backward_mid_chains"] = round(tot_b[0] / a.iters, 3)
