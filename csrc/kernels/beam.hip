@@ -84,9 +84,11 @@ __device__ __forceinline__ void wave_select(float* v, int* id, int n, int K, flo
 // lower bound of the true K-th largest value (the top-K thread maxima are K distinct
 // elements), so every top-K element satisfies x >= tau.  Survivors are appended to LDS
 // and the block's top-K selected from them.  Pathological ties (> FILTER_CAP survivors,
-// e.g. all-equal logits) fall back to a register bubble-insert top-K (LM = 16: K entries of
-// each of the 256 threads fit the FILTER_CAP staging area up to K = 8) or, for the 32-entry
-// list, to a selection in two levels that is exact for every K: a wave's 64 threads stage ALL
+// e.g. all-equal logits) fall back to a register bubble-insert top-K (LM = 16 and K <= 8: K
+// entries of each of the 256 threads fit the FILTER_CAP staging area) or, for the 32-entry list
+// and for K = 9 .. 16, to a selection in two levels that is exact for every K (the insert path
+// at K > 8 staged only threads 0 .. 2048 / K - 1 and lost the maxima the others held:
+// profiles/vocab_head_op_tests.md): a wave's 64 threads stage ALL
 // their 64 * PER_THREAD = FILTER_CAP logits, the wave's best K are selected from them, and the
 // block's best K from the 4 waves' winners (the block's top-K is within the union of the waves'
 // top-K).
@@ -159,7 +161,8 @@ __global__ __launch_bounds__(TOPK_THREADS) void final_topk_partial_kernel(
   const size_t o = ((size_t)r * gridDim.x + sp) * K;
   if (n <= FILTER_CAP) {
     if (tid < 64) wave_select(sv, si, n, K, part_v + o, part_i + o);
-  } else if constexpr (LM <= TOPK_MAX) {  // tie-heavy fallback: exact per-thread insertion then block selection
+  } else if (LM <= TOPK_MAX && TOPK_THREADS * K <= FILTER_CAP) {  // tie-heavy fallback (uniform): exact per-thread
+    // insertion then block selection; K entries of every thread must fit the staging area (K <= 8), else two levels
     Cand c[LM];
 #pragma unroll
     for (int k = 0; k < LM; ++k) c[k] = Cand{-INFINITY, 0x7fffffff};
