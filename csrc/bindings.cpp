@@ -32,6 +32,11 @@ void numel_eq(const Tensor& t, int64_t n, const char* name) {
 void chko(const OT& t, at::ScalarType dt, int64_t n, const char* name) {
   if (t.has_value() && t->defined()) { chk(*t, dt, name); numel_eq(*t, n, name); }
 }
+// a contiguous view at an element offset (a slice of a larger buffer) must still be aligned for the
+// kernel's vector accesses
+void aligned(const Tensor& t, int bytes, const char* name) {
+  TORCH_CHECK((uintptr_t)t.data_ptr() % bytes == 0, name, " must be ", bytes, "-byte aligned");
+}
 const auto F32 = at::kFloat;
 const auto BF = at::kBFloat16;
 const auto I32 = at::kInt;
@@ -443,6 +448,7 @@ void step_frame_hop(const Tensor& in, const Tensor& rev, const Tensor& out, int6
   TORCH_CHECK(H % 4 == 0 && B > 0 && T > 0, "step_frame_hop: H % 4 == 0");
   TORCH_CHECK(rev.scalar_type() == at::kLong && rev.is_contiguous() && rev.numel() == B * T, "rev [B,T] int64");
   numel_eq(in, 2 * T * B * 2 * H, "in"); numel_eq(out, 2 * T * B * H, "out");
+  aligned(in, 16, "step_frame_hop: in"); aligned(out, 16, "step_frame_hop: out");
   launch_step_frame_hop(P<float>(in), rev.data_ptr<int64_t>(), P<float>(out), (int)B, (int)T, (int)H, stream());
 }
 
@@ -462,6 +468,7 @@ void to_step_frame(const Tensor& src, const OT& ids, const Tensor& rev, const Te
     TORCH_CHECK(src.numel() == B * T * S, "src must be [B,T,S] without ids");
   }
   numel_eq(out, 2 * T * B * W, "out");
+  aligned(src, 16, "to_step_frame: src"); aligned(out, 16, "to_step_frame: out");
   launch_to_step_frame(src.data_ptr(), es, PO<int64_t>(ids), P<int64_t>(rev), out.data_ptr(), (int)B, (int)T, (int)W,
                        (int)S, (int)doff, src.numel() / S, stream());
 }
@@ -470,12 +477,15 @@ void from_step_frame(const Tensor& in, const Tensor& rev, const Tensor& out, int
   TORCH_CHECK(rev.scalar_type() == at::kLong && rev.is_contiguous() && rev.numel() == B * T, "rev [B,T] int64");
   TORCH_CHECK(W % 4 == 0, "W % 4");
   numel_eq(in, 2 * T * B * W, "in"); numel_eq(out, B * T * W, "out");
+  aligned(in, 16, "from_step_frame: in"); aligned(out, 16, "from_step_frame: out");
   launch_from_step_frame(P<float>(in), P<int64_t>(rev), P<float>(out), (int)B, (int)T, (int)W, stream());
 }
 void transpose_bta(const Tensor& in, const Tensor& out, int64_t B, int64_t T, int64_t A) {
   chk(in, BF, "in"); chk(out, BF, "out");
   TORCH_CHECK(A % 64 == 0, "A % 64");
   numel_eq(in, B * T * A, "in"); numel_eq(out, B * T * A, "out");
+  aligned(in, 8, "transpose_bta: in");
+  if (T % 4 == 0) aligned(out, 8, "transpose_bta: out");  // the 8-byte stores; any other T stores element by element
   launch_transpose_bta(P<bf16>(in), P<bf16>(out), (int)B, (int)T, (int)A, stream());
 }
 // fp32 [P][Q][R] -> [Q][P][R] fp32 (out) and bf16 (outb), either nullable, one pass
@@ -496,6 +506,7 @@ void cast_colsum(const Tensor& x, const Tensor& xb, const Tensor& colsum, int64_
   chk(x, F32, "x"); chk(xb, BF, "xb"); chk(colsum, F32, "colsum");
   TORCH_CHECK(C % 4 == 0 && C / 4 <= 256 && 256 % (C / 4) == 0, "cast_colsum: C % 4 == 0 and C / 4 divides 256");
   numel_eq(x, N * C, "x"); numel_eq(xb, N * C, "xb"); numel_eq(colsum, C, "colsum");
+  aligned(x, 16, "cast_colsum: x"); aligned(xb, 8, "cast_colsum: xb");
   auto part = at::empty({(int64_t)cast_colsum_blocks((int)N, (int)C), C}, x.options());
   launch_cast_colsum(P<float>(x), P<bf16>(xb), P<float>(part), P<float>(colsum), (int)N, (int)C, stream());
 }
@@ -505,6 +516,7 @@ void colsum(const Tensor& x, const Tensor& out, int64_t N, int64_t C, bool acc) 
               "colsum: x must be a contiguous CUDA fp32 / bf16 tensor");
   chk(out, F32, "out");
   numel_eq(x, N * C, "x"); numel_eq(out, C, "out");
+  if (C % 4 == 0) aligned(x, x.scalar_type() == BF ? 8 : 16, "colsum: x");  // the vector kernel's row loads
   auto part = at::empty({(int64_t)colsum_det_chunks((int)N, (int)C), C}, out.options());
   launch_colsum_det(x.data_ptr(), x.scalar_type() == BF, P<float>(part), P<float>(out), (int)N, (int)C, acc, stream());
 }

@@ -432,6 +432,40 @@ def pack_host_inputs(host: Dict[str, np.ndarray], layout, out: Optional[np.ndarr
     return out
 
 
+def pack_job_rows(pairs, max_jobs: Optional[int] = None):
+    """The pack_cast job rows (pack.hip) of (destination view, fp32 source view[, scale]) pairs and the
+    total workgroup count.  Per pair its kind -- 1 contiguous copy (2048 elements per workgroup), 2
+    transpose of a contiguous matrix (64 x 64 tiles), 3 row-strided rows (2048) or 0 generic strided
+    (256) -- and its first workgroup.  A row is [src, dst, d0..d2, src strides, dst strides, first
+    workgroup, kind, dst is fp32, elements, scale bits].  More than max_jobs pairs: (None, 0), keep
+    the torch path."""
+    if max_jobs is not None and len(pairs) > max_jobs:
+        return None, 0
+    rows, blk = [], 0
+    for dst, src, *scale in pairs:
+        assert dst.shape == src.shape and src.dtype == F32 and dst.dtype in (BF, F32) and dst.dim() <= 3, \
+            (dst.shape, src.shape)
+        shape = [1] * (3 - dst.dim()) + list(dst.shape)
+        ss = [0] * (3 - src.dim()) + list(src.stride())
+        ts = [0] * (3 - dst.dim()) + list(dst.stride())
+        n = dst.numel()
+        if dst.is_contiguous() and src.is_contiguous() and src.data_ptr() % 32 == 0 and dst.data_ptr() % 16 == 0:
+            kind, nblk = 1, -(-n // 2048)
+        elif (dst.dim() == 2 and dst.is_contiguous() and src.stride() == (1, src.shape[0])):
+            R, C = dst.shape  # src = the transpose view of a contiguous [C][R] matrix
+            kind, nblk = 2, -(-R // 64) * -(-C // 64)
+        elif (dst.dim() == 2 and dst.stride(1) == 1 and src.stride(1) == 1 and dst.shape[1] % 8 == 0
+              and dst.stride(0) % 8 == 0 and src.stride(0) % 4 == 0 and src.data_ptr() % 16 == 0
+              and dst.data_ptr() % 16 == 0):
+            kind, nblk = 3, -(-n // 2048)  # row-strided rows (e.g. the [H][Vp] padded W): 8 per thread
+        else:
+            kind, nblk = 0, -(-n // 256)
+        sc = int(np.array(scale[0], dtype=np.float32).view(np.int32)) if scale else 0  # fp32 bits, 0 = 1.0
+        rows.append([src.data_ptr(), dst.data_ptr(), *shape, *ss, *ts, blk, kind, int(dst.dtype == F32), n, sc])
+        blk += nblk
+    return rows, blk
+
+
 class HipPointerGenerator:
     """Fixed-shape (B rows, T encoder steps, D decoder steps) train/eval engine."""
 
@@ -798,29 +832,8 @@ class HipPointerGenerator:
         strided (256) -- and its first workgroup."""
         E = self.E
         self._wcomb = torch.mm(self.p[LIN_M][E:], self.p[CELL_K][:E])
-        rows, blk = [], 0
-        for dst, src, *scale in self._pack_job_pairs():
-            assert dst.shape == src.shape and src.dtype == F32 and dst.dtype in (BF, F32) and dst.dim() <= 3, \
-                (dst.shape, src.shape)
-            shape = [1] * (3 - dst.dim()) + list(dst.shape)
-            ss = [0] * (3 - src.dim()) + list(src.stride())
-            ts = [0] * (3 - dst.dim()) + list(dst.stride())
-            n = dst.numel()
-            if dst.is_contiguous() and src.is_contiguous() and src.data_ptr() % 32 == 0 and dst.data_ptr() % 16 == 0:
-                kind, nblk = 1, -(-n // 2048)
-            elif (dst.dim() == 2 and dst.is_contiguous() and src.stride() == (1, src.shape[0])):
-                R, C = dst.shape  # src = the transpose view of a contiguous [C][R] matrix
-                kind, nblk = 2, -(-R // 64) * -(-C // 64)
-            elif (dst.dim() == 2 and dst.stride(1) == 1 and src.stride(1) == 1 and dst.shape[1] % 8 == 0
-                  and dst.stride(0) % 8 == 0 and src.stride(0) % 4 == 0 and src.data_ptr() % 16 == 0
-                  and dst.data_ptr() % 16 == 0):
-                kind, nblk = 3, -(-n // 2048)  # row-strided rows (e.g. the [H][Vp] padded W): 8 per thread
-            else:
-                kind, nblk = 0, -(-n // 256)
-            sc = int(np.array(scale[0], dtype=np.float32).view(np.int32)) if scale else 0  # fp32 bits, 0 = 1.0
-            rows.append([src.data_ptr(), dst.data_ptr(), *shape, *ss, *ts, blk, kind, int(dst.dtype == F32), n, sc])
-            blk += nblk
-        if len(rows) > int(self.k.pack_max_jobs()) or len(rows[0]) != int(self.k.pack_job_cols()):
+        rows, blk = pack_job_rows(self._pack_job_pairs(), int(self.k.pack_max_jobs()))
+        if rows is None or len(rows[0]) != int(self.k.pack_job_cols()):
             return  # keep the torch path
         self._pack_jobs = torch.tensor(rows, dtype=torch.long, device=self.dev)
         self._pack_total = blk
