@@ -5,7 +5,7 @@ dimension, beta = 1 accumulation, fp32 / bf16 bias epilogues, bf16 output."""
 import pytest
 import torch
 
-from textsummarization_on_flink_amd.models.pointer_generator import gemm
+from textsummarization_on_flink_amd.models.gemm_dispatch import gemm
 from textsummarization_on_flink_amd.ops import ops
 from textsummarization_on_flink_amd.utils.graphs import capture_guard
 

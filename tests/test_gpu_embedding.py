@@ -31,7 +31,7 @@ import numpy as np
 import pytest
 import torch
 
-from textsummarization_on_flink_amd.models.pointer_generator import emb_sort
+from textsummarization_on_flink_amd.models.host_inputs import emb_sort
 from textsummarization_on_flink_amd.ops import ops
 
 pytestmark = pytest.mark.gpu

@@ -278,7 +278,7 @@ DLEN = {"A": [12, 9, 3, 6, 1],     # blocks 0 and 1 live, block 2 (rows 64..69) 
 
 
 def _blocks(dlen, D):
-    """vlive / vblk / vblk_n of the 32-row blocks, as host_inputs (models/pointer_generator.py)
+    """vlive / vblk / vblk_n of the 32-row blocks, as host_inputs (models/host_inputs.py)
     builds them from the live decoder steps per row."""
     dlen = np.asarray(dlen)
     nb = (D * len(dlen) + 31) // 32

@@ -44,16 +44,17 @@ def _batches(hps, n, seed):
     return vocab, make_batches(hps, vocab, corpus, n, pad_enc_to=T)
 
 
-def _oracle_check(hps, B, T_, D_, seed, cov_tol=2e-2):
-    """One forward + backward of the HIP engine vs the fp32 oracle (autograd) on the same GPU:
-    loss, coverage loss, attention distributions, p_gen and every parameter gradient."""
+def _oracle_check(hps, B, T_, D_, seed, cov_tol=2e-2, cfg=None):
+    """One forward + backward of the HIP engine (``cfg``: its EngineConfig, default from the
+    environment) vs the fp32 oracle (autograd) on the same GPU: loss, coverage loss, attention
+    distributions, p_gen and every parameter gradient."""
     from textsummarization_on_flink_amd.models.pointer_generator import HipPointerGenerator
     corpus = SyntheticCorpus(vocab_size=hps.vocab_size, seed=seed)
     vocab = corpus.vocab(hps.vocab_size)
     (batch,) = make_batches(hps, vocab, corpus, 1, pad_enc_to=T_)
     params = build_params(hps, vocab.size(), device="cuda", seed=3)
     params.enable_grad()
-    eng = HipPointerGenerator(hps, vocab.size(), params, B=B, T=T_, D=D_)
+    eng = HipPointerGenerator(hps, vocab.size(), params, B=B, T=T_, D=D_, cfg=cfg)
     eng.set_batch(batch)
     out = eng.forward(need_grad=True)
     eng.backward()
@@ -90,23 +91,22 @@ def test_bench_shape_with_every_weight_gradient_on_wgrad_tt(monkeypatch):
     deterministic split-K wgrad_tt (threshold 0; deterministic mode runs the decoder-side ones
     inline, where they take it too): encoder x^T.dz / h^T.dz (K = T.B = 102400, layer 0's M = 128
     with the operand roles swapped), decoder cell / output-projection / attention / W_h (K = D.B)."""
-    from textsummarization_on_flink_amd.models import pointer_generator as pgm
-    monkeypatch.setattr(pgm, "WGRAD_TT_MIN", 0)
+    from textsummarization_on_flink_amd.models import gemm_dispatch
+    monkeypatch.setattr(gemm_dispatch, "WGRAD_TT_MIN", 0)
     monkeypatch.setenv("TSAMD_DETERMINISTIC", "1")
     _oracle_check(_hps(256, trunc_norm_init_std=0.05), 256, T, D, seed=13)
 
 
-def test_bench_shape_with_vocab_dw_on_the_split_bmm_and_unpadded(monkeypatch):
+def test_bench_shape_with_vocab_dw_on_the_split_bmm_and_unpadded():
     """The vocab weight gradient's other paths against the fp32 oracle: the 4-way split-K batched
     GEMM over the padded dlogits rows (config #5's path, threshold 0 here), and the unpadded
-    layout (TSAMD_VOCAB_PAD=0: the round-5 GEMMs at V = 50k)."""
-    from textsummarization_on_flink_amd.models import pointer_generator as pgm
-    monkeypatch.setattr(pgm, "VOCAB_DW_SPLIT_MIN", 0)
-    _oracle_check(_hps(256, trunc_norm_init_std=0.05), 256, T, D, seed=17)
-    monkeypatch.setattr(pgm, "VOCAB_PAD", False)
-    monkeypatch.setattr(pgm, "DE_BF16", False)
-    monkeypatch.setattr(pgm, "CTX_NATIVE", False)
-    _oracle_check(_hps(256, trunc_norm_init_std=0.05), 256, T, D, seed=19)
+    layout (EngineConfig.vocab_pad off: the round-5 GEMMs at V = 50k; the split threshold is not
+    read there)."""
+    from textsummarization_on_flink_amd.models.engine_config import EngineConfig
+    _oracle_check(_hps(256, trunc_norm_init_std=0.05), 256, T, D, seed=17,
+                  cfg=EngineConfig.from_env(vocab_dw_split_min=0))
+    _oracle_check(_hps(256, trunc_norm_init_std=0.05), 256, T, D, seed=19,
+                  cfg=EngineConfig.from_env(vocab_pad=False, de_bf16=False, ctx_native=False))
 
 
 def test_bench_shape_matches_fp32_oracle():
@@ -382,7 +382,7 @@ def test_vocab_dw_beside_decoder_loop_matches_inline(monkeypatch, det):
     monkeypatch.setenv("TSAMD_DETERMINISTIC", det)
     res = []
     for side in (False, True):
-        monkeypatch.setattr(trm, "VOCAB_DW_SIDE", side)
+        monkeypatch.setenv("TSAMD_VOCAB_DW_SIDE", "1" if side else "0")  # read when the trainer builds its engine
         tr = trm.GraphTrainer(hps, vocab.size(), B=B, T=T, device="cuda:0")
         assert tr.dw_side == side
         for i in range(4):

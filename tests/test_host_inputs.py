@@ -1,4 +1,4 @@
-"""Host-side engine inputs (models/pointer_generator.host_inputs), CPU only: the live decoder
+"""Host-side engine inputs (models/host_inputs.py), CPU only: the live decoder
 steps per row, the row order sorted by them (every per-row array permuted consistently, the
 loss weights unchanged as a multiset), and the fused vocab head's live-block list -- the inputs
 the skipping kernels trust (EngineConfig.skip_pad_steps)."""
@@ -7,7 +7,7 @@ import pytest
 
 from textsummarization_on_flink_amd.config import HParams
 from textsummarization_on_flink_amd.data.synthetic import SyntheticCorpus, make_batches
-from textsummarization_on_flink_amd.models.pointer_generator import host_inputs, input_layout, pack_host_inputs
+from textsummarization_on_flink_amd.models.host_inputs import host_inputs, input_layout, pack_host_inputs
 
 
 def _batch(B=24, T=60, D=30, pointer_gen=True, seed=3):
@@ -72,7 +72,7 @@ def test_gemm_dispatch_table_is_fixed_by_shape():
     """The activation-GEMM dispatch (TSAMD_GEMM_BT=table, the default) depends only on the shape:
     the hand-written GEMM for step-frame gathers, K <= 256 and bf16-out K <= 1024; hipBLASLt for
     the fp32-out K >= 512 shapes -- the same pick on every run and rank (profiles/r6/gemm_dispatch.md)."""
-    from textsummarization_on_flink_amd.models import pointer_generator as pg
+    from textsummarization_on_flink_amd.models import gemm_dispatch as pg
     assert pg.GEMM_BT in ("table", "auto", "0", "1")
     rule = pg._bt_rule
     assert rule(128, False, 1.0) and rule(256, False, 1.0)
@@ -85,7 +85,7 @@ def test_gemm_dispatch_table_is_fixed_by_shape():
 def test_encoder_wgrad_cpu_path_matches_matmul():
     """wgrad_enc_into on CPU tensors (the oracle backend) falls back to the plain matmul path."""
     import torch
-    from textsummarization_on_flink_amd.models.pointer_generator import wgrad_enc_into
+    from textsummarization_on_flink_amd.models.gemm_dispatch import wgrad_enc_into
     g = torch.Generator().manual_seed(0)
     a, b = torch.randn(64, 16, generator=g), torch.randn(64, 24, generator=g)
     out = torch.empty(16, 24)

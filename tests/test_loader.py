@@ -8,7 +8,7 @@ from textsummarization_on_flink_amd.data import binfmt
 from textsummarization_on_flink_amd.data.batch import Batch, Example
 from textsummarization_on_flink_amd.data.loader import ProcessBatcher
 from textsummarization_on_flink_amd.data.vocab import Vocab, abstract2sents
-from textsummarization_on_flink_amd.models.pointer_generator import host_inputs, input_layout, pack_host_inputs
+from textsummarization_on_flink_amd.models.host_inputs import host_inputs, input_layout, pack_host_inputs
 
 from helpers import make_dataset
 

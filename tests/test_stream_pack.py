@@ -14,7 +14,7 @@ from textsummarization_on_flink_amd.data.batcher import FlinkTrainBatcher, IterR
 from textsummarization_on_flink_amd.data.stream_pack import StreamDecodePacker, StreamTrainPacker
 from textsummarization_on_flink_amd.data.synthetic import SyntheticCorpus
 from textsummarization_on_flink_amd.decode.decoder import flink_summary
-from textsummarization_on_flink_amd.models.pointer_generator import host_inputs, input_layout, pack_host_inputs
+from textsummarization_on_flink_amd.models.host_inputs import host_inputs, input_layout, pack_host_inputs
 from textsummarization_on_flink_amd.runtime.ring import RecordRing, RingPipe
 
 IN_COLS = ["uuid", "article", "reference"]

@@ -79,7 +79,7 @@ def _push(ring, data: bytes) -> None:
 
 def _worker(w: int, n: int, ring_name: str, data_path: str, vocab: Vocab, hps, single_pass: bool, seed: int,
             pad_enc_to: Optional[int], D: int, cache: int, rank: int = 0, world: int = 1) -> None:
-    from ..models.pointer_generator import host_inputs, input_layout, pack_host_inputs
+    from ..models.host_inputs import host_inputs, input_layout, pack_host_inputs
     from ..runtime.ring import RecordRing, RingClosed
     ring = RecordRing.open(ring_name)
     B, T = hps.batch_size, pad_enc_to or hps.max_enc_steps

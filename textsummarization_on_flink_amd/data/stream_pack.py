@@ -196,7 +196,7 @@ def _report(ring, e: BaseException):
 
 # ---------------------------------------------------------------------- training
 def _train_packer(p: int, n: int, names: List[str], coding, vocab, hps, T: int, D: int) -> None:
-    from ..models.pointer_generator import host_inputs, input_layout, pack_host_inputs
+    from ..models.host_inputs import host_inputs, input_layout, pack_host_inputs
     from ..runtime.ring import RecordRing, RingClosed
     rin, rout = RecordRing.open(names[0]), RecordRing.open(names[1])
     B = hps.batch_size
@@ -446,7 +446,7 @@ class StreamDecodePacker:
     def __init__(self, in_ring, out_ring, coding, out_coding, vocab, hps, packers: int, n_articles: int, T: int,
                  max_wait_s: float, ring_bytes: int = 32 << 20):
         from ..data.vocab import PAD_TOKEN, START_DECODING
-        from ..models.pointer_generator import input_layout
+        from ..models.host_inputs import input_layout
         from ..runtime.ring import RingPipe
         self.Na, self.T, self.max_wait_s = n_articles, T, max_wait_s
         self.hb = hps.replace(batch_size=n_articles)
@@ -488,7 +488,7 @@ class StreamDecodePacker:
                 self._rr = (self._rr + 1) % len(self._live)
 
     def poll(self, block: bool):
-        from ..models.pointer_generator import host_inputs, pack_host_inputs
+        from ..models.host_inputs import host_inputs, pack_host_inputs
         items, owners = [], []
         self._gather(items, owners)
         if not items:

@@ -31,8 +31,9 @@ import torch
 
 from ..data.vocab import START_DECODING, STOP_DECODING, UNKNOWN_TOKEN
 from ..models.pointer_generator import (ATT_B, CELL_B, CELL_K, EMB, LIN_B, LIN_M, OUT_B, OV, PG_B, PG_M,
-                                        HipPointerGenerator, mmf)
+                                        HipPointerGenerator)
 from ..models.engine_config import EngineConfig
+from ..models.gemm_dispatch import mmf
 from ..utils.graphs import capture_guard
 from ..config import check_penalties
 from .beam_search import Hypothesis, inv_len_table, penalties_on

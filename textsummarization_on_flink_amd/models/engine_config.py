@@ -21,7 +21,18 @@ engine is built); code can also pass a config explicitly.
 | TSAMD_COMPACT_VOCAB_GRAD  | compact_vocab_grad | 1: with skip_pad_steps, the vocab-head dlogits of the live 32-row blocks are written compacted and the two gradient GEMMs run over those rows only (bucketed block counts); 0: every row |
 | TSAMD_DEFER_WGRAD         | defer_wgrad        | 1: decoder-side weight gradients beside the encoder BPTT (B >= 256); 0: inline |
 | TSAMD_DETERMINISTIC       | deterministic      | 0; 1: fixed-order reductions instead of fp32 atomics (bit-reproducible steps) |
+| TSAMD_VOCAB_PAD           | vocab_pad          | 1 (fused vocab head): dlogits rows and the bf16 output-projection weight padded to Vp = 128-aligned columns (the pad columns stay zero: allocated zeroed, never written), so the two vocab-gradient GEMMs run at an aligned K / N -- dX = dlogits . W^T on the split-K hand-written GEMM (headline: 566 -> 426 us) or the library (config #5: 7.88 -> 6.76 ms), dW = X^T . dlogits on the library into a [H][Vp] scratch (653 -> 502 us with the copy) (tools/vocab_grad_micro.py, profiles/r6/vocab_grad.md); 0: unpadded [N][V] |
+| TSAMD_CTX_NATIVE          | ctx_native         | 1: the three batched attention-context GEMMs (ctx = a . enc_out, its gradients dA = dctx . enc_out^T and dE = a^T . dctx) on the hand-written ctx_bmm.hip kernels (step-major outputs, no tr01 pass); 0: torch.bmm + tr01 |
+| TSAMD_DE_BF16             | de_bf16            | 1 (with the native context kernels and the persistent BPTT): the encoder-output gradient dE = a^T . dctx + dF . W_h^T kept in bf16 -- ctx_de writes a^T . dctx in bf16, the W_h GEMM adds into it (beta = 1, bf16 in and out), the top layer's BPTT reads it; 0: an fp32 [B][T][A] buffer written, re-read and rewritten, and read again (profiles/r6/de_bf16.md) |
+| TSAMD_DX_MERGE            | dx_merge           | 1: the input gradients of an upper encoder layer as one hand-written GEMM per output direction over the concatenated [dz_fw, dz_bw], rows gathered through the reversed index, written straight into the lower layer's step frame (gemm_mfma.hip AMODE 2; needs ``gemm_dispatch.BLT`` and ``GEMM_BT`` != "0"); 0: two per-direction GEMMs + step_frame_hop.  Config #5 at batch 2048: same step time (391.8 vs 391.9 ms), 14 GB less memory (no per-direction dxs).  Layer 0 keeps the library GEMMs + from_step_frame: its merged GEMM (N = E = 128, one 128-column tile) measured 0.1 ms slower at batch 256 (profiles/r5/dx_merge.md) |
+| TSAMD_LSTM_FX             | lstm_fx            | 1: encoder layer 0's input projection x.W_x inside the persistent recurrence (lstm_persistent.hip FX): the step-frame inputs (bf16, E = 128) are gathered once and each step's x MFMAs run in the shadow of the hand-off wait -- no gx GEMM, no gx buffer; 0: a GEMM writes gx (fp32 [2][T][B][4H]) before the recurrence |
+| TSAMD_VOCAB_DW_SIDE       | vocab_dw_side      | 0; 1 (graph trainer): the vocab weight gradient dW = X^T . dlogits leaves the vocab-backward graph for a graph of its own, replayed on a side stream beside the decoder backward loop (train/trainer.py _Phase1).  Measured at the headline: phase 0 -0.4 ms, phase 1 +0.4 ms -- the loop's step kernels wait behind the GEMM's workgroups and share its HBM stream; CU-masked and low-priority side streams were slower still (profiles/r6/vocab_dw_side.md) |
+| TSAMD_BLT_VOCAB_DW        | blt_vocab_dw       | 0: the vocab dW as a split-K batched GEMM; 1: through blt_mm (effective only with ``gemm_dispatch.BLT``) |
+| (none)                    | vocab_dw_split_min | 1e12: K.M.N above which the padded vocab dW keeps the 4-way split-K batched GEMM (config #5: 8.2 ms against 9.5 ms for the library at the padded N) |
 | TSAMD_KERNEL_DEBUG        | (ops loader)       | 0; 1: the bounds-checked kernel library ``_C_debug.so`` |
+
+The process-wide GEMM switches (TSAMD_BLT, TSAMD_BLT_WGRAD, TSAMD_GEMM_BT, TSAMD_WGRAD_TT,
+TSAMD_WGRAD_TT_MIN) are globals of ``gemm_dispatch``, read at its import.
 """
 from __future__ import annotations
 
@@ -40,6 +51,11 @@ def _tri(env: Mapping[str, str], name: str) -> Optional[bool]:
     return None if v == "" else v != "0"
 
 
+def _on(env: Mapping[str, str], name: str) -> bool:
+    """A switch that is off by default and on only at "1"."""
+    return env.get(name, "0") == "1"
+
+
 @dataclass(frozen=True)
 class EngineConfig:
     persistent_lstm: bool = True
@@ -56,6 +72,14 @@ class EngineConfig:
     compact_vocab_grad: bool = True
     defer_wgrad: bool = True
     deterministic: bool = False
+    vocab_pad: bool = True
+    ctx_native: bool = True
+    de_bf16: bool = True
+    dx_merge: bool = True
+    lstm_fx: bool = True
+    vocab_dw_side: bool = False
+    blt_vocab_dw: bool = False
+    vocab_dw_split_min: float = 1e12
 
     @classmethod
     def from_env(cls, env: Optional[Mapping[str, str]] = None, **overrides) -> "EngineConfig":
@@ -75,6 +99,13 @@ class EngineConfig:
             compact_vocab_grad=_flag(env, "TSAMD_COMPACT_VOCAB_GRAD", True),
             defer_wgrad=_flag(env, "TSAMD_DEFER_WGRAD", True),
             deterministic=_flag(env, "TSAMD_DETERMINISTIC", False),
+            vocab_pad=_flag(env, "TSAMD_VOCAB_PAD", True),
+            ctx_native=_flag(env, "TSAMD_CTX_NATIVE", True),
+            de_bf16=_flag(env, "TSAMD_DE_BF16", True),
+            dx_merge=_flag(env, "TSAMD_DX_MERGE", True),
+            lstm_fx=_flag(env, "TSAMD_LSTM_FX", True),
+            vocab_dw_side=_on(env, "TSAMD_VOCAB_DW_SIDE"),
+            blt_vocab_dw=_on(env, "TSAMD_BLT_VOCAB_DW"),
         )
         return replace(cfg, **overrides) if overrides else cfg
 

@@ -1,36 +1,44 @@
 """MI355X production path of the pointer-generator network (train / eval).
 
-The step is written as an explicit forward + hand-derived backward over preallocated
-buffers (no autograd graph, no per-step allocation), so ``train_step`` is a fixed
-sequence of launches on one stream that ``torch.cuda.graph`` captures once and replays
-(hipGraph): per step ~8 kernels x D decoder steps and 2 kernels x T encoder steps, each
-paying only the ~1.5 us dependent-kernel boundary instead of ~10 us of Python dispatch.
+The step is an explicit forward + hand-derived backward over preallocated buffers (no autograd
+graph, no per-step allocation): a fixed sequence of launches that the graph trainer captures once
+as a few phase graphs (hipGraph) and replays (train/trainer.py).
 
 Where the work goes:
-  * recurrences (encoder bi-LSTM, decoder cell, attention) -> hand-written gfx950 kernels
-    (``csrc/kernels/{lstm,decoder,attention}.hip``), one launch per time step;
-  * vocab distribution + pointer mixture + NLL -> fused kernel (``loss.hip``) that never
-    materialises the [N, V+O] final distribution;
+  * encoder bi-LSTM -> one persistent weight-resident launch per pass (``lstm_persistent.hip``;
+    per-step kernels of ``lstm.hip`` when ``EngineConfig.persistent_lstm`` is off);
+  * decoder cell + attention, forward and backward loop -> one persistent launch each where
+    eligible (``decoder_persistent.hip``, ``decoder_bwd_persistent.hip``), else three launches
+    per step and row group (``decoder.hip``, ``attention*.hip``);
+  * vocab distribution + pointer mixture + NLL -> the fused vocab head (``vocab_train.hip``:
+    logits only in MFMA accumulators, the [N, V] buffer receives dlogits), or the library GEMM
+    + ``loss.hip`` ptr_loss; neither materialises the [N, V+O] final distribution;
   * every hoistable GEMM (input projections for all T, W_h features, p_gen / output
-    projections for all D, vocab projection, all weight gradients) -> one big bf16 GEMM
-    each (hipBLASLt, the fastest candidate per shape: ``gemm`` / csrc/blt_gemm.cpp; fp32
-    accumulate/output);
+    projections for all D, the vocab gradients, all weight gradients) -> one bf16 GEMM each,
+    hipBLASLt or a hand-written kernel per shape (``gemm_dispatch.py``);
+  * the per-batch host inputs -> ``host_inputs.py`` (numpy; loader processes build them too);
   * clip + Adagrad -> fused kernel over the flat parameter buffer (``optim.hip``).
+
+Every switch of the engine is an ``EngineConfig`` field, read when an engine is built; this
+module reads no environment variable.
 
 Reference semantics: ``model.py:76-305``, ``attention_decoder.py:27-180``.
 """
 from __future__ import annotations
 
-
-import os
-from typing import Dict, List, Optional
+from typing import Dict, Optional
 
 import numpy as np
 import torch
 
 from ..ops import ops as _ops
 from ..parallel.rccl_env import rccl_cu_reserve
+from . import gemm_dispatch
 from .engine_config import EngineConfig, dec_bwd_persistent_eligible, dec_persistent_eligible, handoff_error_message
+from .gemm_dispatch import BLT, gemm_bt_stats  # noqa: F401  (kept here only because bench.py reads them here)
+from .gemm_dispatch import FRAME_SLACK, K2LOG2E, _use_bt, gemm, mm_into, mmf, wgrad_enc_into
+from .host_inputs import emb_sort  # noqa: F401  (a function, kept importable from here for callers of before the split)
+from .host_inputs import host_inputs, input_layout, pack_host_inputs
 from .params import DEC, P, FlatParams, enc_prefix
 
 BF = torch.bfloat16
@@ -58,378 +66,6 @@ def enc_k(layer, d):
 
 def enc_b(layer, d):
     return f"{enc_prefix(layer)}/bidirectional_rnn/{d}/lstm_cell/bias"
-
-
-# TSAMD_BLT=0: library GEMMs through torch.mm (hipBLASLt's first heuristic pick) instead of
-# blt_mm (csrc/blt_gemm.cpp: hipBLASLt called directly, the fastest of its candidates per shape)
-BLT = os.environ.get("TSAMD_BLT", "1") != "0"
-# the long-K weight gradients (encoder, vocab dW) through blt_mm too (default: split-K batched GEMM)
-BLT_WGRAD = BLT and os.environ.get("TSAMD_BLT_WGRAD", "0") == "1"
-BLT_VDW = BLT and os.environ.get("TSAMD_BLT_VOCAB_DW", "0") == "1"
-# TSAMD_VOCAB_PAD (default 1, fused vocab head): dlogits rows and the bf16 output-projection weight
-# padded to Vp = 128-aligned columns (the pad columns stay zero: allocated zeroed, never written), so
-# the two vocab-gradient GEMMs run at an aligned K / N -- dX = dlogits . W^T on the split-K
-# hand-written GEMM (headline: 566 -> 426 us) or the library (config #5: 7.88 -> 6.76 ms),
-# dW = X^T . dlogits on the library into a [H][Vp] scratch (653 -> 502 us with the copy)
-# (tools/vocab_grad_micro.py, profiles/r6/vocab_grad.md)
-VOCAB_PAD = os.environ.get("TSAMD_VOCAB_PAD", "1") != "0"
-# TSAMD_CTX_NATIVE (default 1): the three batched attention-context GEMMs (ctx = a . enc_out, its
-# gradients dA = dctx . enc_out^T and dE = a^T . dctx) on the hand-written ctx_bmm.hip kernels
-# (step-major outputs, no tr01 pass) instead of torch.bmm + tr01
-CTX_NATIVE = os.environ.get("TSAMD_CTX_NATIVE", "1") != "0"
-# TSAMD_DE_BF16 (default 1; with the native context kernels and the persistent BPTT): the encoder-
-# output gradient dE = a^T . dctx + dF . W_h^T kept in bf16 -- ctx_de writes a^T . dctx in bf16, the
-# W_h GEMM adds into it (beta = 1, bf16 in and out), the top layer's BPTT reads it -- instead of an
-# fp32 [B][T][A] buffer written, re-read and rewritten, and read again (profiles/r6/de_bf16.md)
-DE_BF16 = os.environ.get("TSAMD_DE_BF16", "1") != "0"
-# K.M.N above which the vocab dW keeps the 4-way split-K batched GEMM (config #5: 8.2 ms against
-# 9.5 ms for the library at the padded N)
-VOCAB_DW_SPLIT_MIN = 1e12
-# TSAMD_VOCAB_DW_SIDE=1 (graph trainer; default 0): the vocab weight gradient dW = X^T . dlogits
-# leaves the vocab-backward graph for a graph of its own, replayed on a side stream beside the
-# decoder backward loop (train/trainer.py _Phase1).  Measured at the headline: phase 0 -0.4 ms,
-# phase 1 +0.4 ms -- the loop's step kernels wait behind the GEMM's workgroups and share its HBM
-# stream; CU-masked and low-priority side streams were slower still (profiles/r6/vocab_dw_side.md)
-VOCAB_DW_SIDE = os.environ.get("TSAMD_VOCAB_DW_SIDE", "0") == "1"
-
-
-# TSAMD_GEMM_BT: the hand-written MFMA GEMM (csrc/kernels/gemm_mfma.hip) for the activation GEMMs
-# whose weight operand has a [N][K] twin.  "table" (default): a fixed per-shape rule from the
-# recorded head-to-head timings (``_bt_rule``; profiles/r5/gemm_micro_v3.jsonl,
-# profiles/r6/gemm_dispatch.md) -- the same pick on every run, box and rank; "auto" times it
-# against blt_mm once per shape on the first eager call and keeps the faster (the round-5 default:
-# picks could differ between runs); "1" always where eligible (deterministic mode too); "0" never
-GEMM_BT = os.environ.get("TSAMD_GEMM_BT", "table")
-_BT_PICK: Dict[tuple, bool] = {}
-_BT_TIMES: Dict[tuple, tuple] = {}
-# TSAMD_DX_MERGE=0: the input gradients of an upper encoder layer as two per-direction GEMMs +
-# step_frame_hop (default: one hand-written GEMM per output direction over [dz_fw | dz_bw], rows
-# gathered through the reversed index, written straight into the lower layer's step frame --
-# gemm_mfma.hip AMODE 2).  Config #5 at batch 2048: same step time (391.8 vs 391.9 ms), 14 GB less
-# memory (no per-direction dxs).  Layer 0 keeps the library GEMMs + from_step_frame: its merged
-# GEMM (N = E = 128, one 128-column tile) measured 0.1 ms slower at batch 256
-# (profiles/r5/dx_merge.md).
-DX_MERGE = os.environ.get("TSAMD_DX_MERGE", "1") != "0"
-# TSAMD_LSTM_FX=0: encoder layer 0's input projection x.W_x as a GEMM writing gx (fp32
-# [2][T][B][4H]) before the persistent recurrence.  Default: inside the recurrence
-# (lstm_persistent.hip FX): the step-frame inputs (bf16, E = 128) are gathered once and each
-# step's x MFMAs run in the shadow of the hand-off wait -- no gx GEMM, no gx buffer.
-LSTM_FX = os.environ.get("TSAMD_LSTM_FX", "1") != "0"
-# 2 log2(e): the attention features F = enc_out . W_h are stored multiplied by it (the kernels'
-# tanh argument is 2^(K u); attn_common.h fadd_bf2)
-K2LOG2E = 2.8853900817779268
-# the step-frame gather path replaces to_step_frame + the GEMM: kept while the gather GEMM is at
-# most this much slower than the library GEMM alone (the layout pass it saves costs ~25-40 % of it)
-FRAME_SLACK = 1.25
-
-
-def _aligned(t: torch.Tensor) -> bool:
-    return t.stride(-1) == 1 and (t.dim() < 2 or t.stride(0) % 8 == 0) and t.data_ptr() % 16 == 0
-
-
-def _bt_ok(out, sa, ta, Bt, beta, bias) -> bool:
-    return (GEMM_BT != "0" and Bt is not None and not ta and Bt.dtype == BF and out.is_cuda and _aligned(sa)
-            and _aligned(Bt) and _aligned(out) and beta in (0.0, 1.0) and not (beta and out.dtype == BF)
-            and (bias is None or (bias.dtype == F32 and bias.is_contiguous()))
-            and bool(_ops().gemm_bt_ok(out.shape[0], out.shape[1], Bt.shape[1])) and sa.shape[1] == Bt.shape[1])
-
-
-def _deterministic() -> bool:
-    return os.environ.get("TSAMD_DETERMINISTIC", "0") not in ("", "0")
-
-
-def _time_us(fn, reps: int = 3) -> float:
-    fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1000.0 / reps
-
-
-def _bt_timed(out, sa, Bt, beta, bias, sb, tb):
-    """(gemm_bt us, blt_mm us) of this shape on a row subset (<= 131072 rows) into scratch."""
-    key = (tuple(out.shape), out.dtype, sa.shape[1], beta != 0.0, bias is not None, sa.stride(0), Bt.stride(0))
-    if key not in _BT_TIMES:
-        m = min(out.shape[0], 131072)
-        a, o = sa[:m], torch.empty(m, out.shape[1], dtype=out.dtype, device=out.device)
-        k = _ops()
-        t_bt = _time_us(lambda: k.gemm_bt(a, Bt, o, float(beta), bias, None, None, 0, 0, 0, None))
-        t_blt = _time_us(lambda: k.blt_mm(a, sb, o, False, tb, float(beta), bias))
-        _BT_TIMES[key] = (t_bt, t_blt)
-    return _BT_TIMES[key]
-
-
-def _bt_rule(K: int, out_bf16: bool, slack: float) -> bool:
-    """The fixed dispatch (TSAMD_GEMM_BT=table), from the head-to-head records
-    (profiles/r5/gemm_micro_v3.jsonl and the round-6 timed picks, profiles/r6/gemm_dispatch.md):
-    the hand-written GEMM wins every K <= 256 shape (b256_gx 104 vs 112 us, c5_gx_l0 1340 vs 1443,
-    25600 x 128 x 128 8.1 vs 16.2), the bf16-out shapes up to K = 1024 (25600 x 512 x 512 22.2 vs
-    29.1, c5_F 1694 vs 1707; b256_F measured both ways across runs) and loses the fp32-out
-    K >= 512 shapes (25600 x 256 x 512 28.1 vs 20.4, 102400 x 512 x 512 154 vs 117, c5_dx_l1 3380
-    vs 3010) -- within FRAME_SLACK where it also saves the step-frame layout pass."""
-    return slack > 1.0 or K <= 256 or (out_bf16 and K <= 1024)
-
-
-def _use_bt(out, sa, ta, Bt, beta, bias, sb, tb, slack: float = 1.0) -> bool:
-    if not _bt_ok(out, sa, ta, Bt, beta, bias):
-        return False
-    if GEMM_BT == "1" or _deterministic():
-        return True
-    key = (tuple(out.shape), out.dtype, sa.shape[1], beta != 0.0, bias is not None, sa.stride(0), Bt.stride(0), slack)
-    if key not in _BT_PICK:
-        if GEMM_BT != "auto":
-            _BT_PICK[key] = _bt_rule(sa.shape[1], out.dtype == BF, slack)
-        elif torch.cuda.is_current_stream_capturing():
-            return False  # first seen inside a capture: no timing possible, keep the library GEMM
-        else:
-            t_bt, t_blt = _bt_timed(out, sa, Bt, beta, bias, sb, tb)
-            _BT_PICK[key] = t_bt <= slack * t_blt
-    return _BT_PICK[key]
-
-
-def gemm_bt_stats() -> Dict[str, object]:
-    """The hand-written-GEMM dispatch: mode, every shape seen (M x N x K, out dtype, frame
-    gather) with the kernel it got, and (mode "auto") the timings behind the picks."""
-    picks = {f"{k[0][0]}x{k[0][1]}x{k[2]}{'_bf16' if k[1] == BF else ''}{'_frame' if k[7] > 1.0 else ''}":
-             ("gemm_bt" if v else "hipblaslt") for k, v in _BT_PICK.items()}
-    return {"mode": "deterministic" if _deterministic() else GEMM_BT, "shapes": len(_BT_PICK),
-            "gemm_bt": int(sum(_BT_PICK.values())), "picks": picks,
-            "timed_us": {f"{k[0][0]}x{k[0][1]}x{k[2]}": [round(v[0], 1), round(v[1], 1)] for k, v in _BT_TIMES.items()}}
-
-
-def _stored(x: torch.Tensor):
-    """(row-contiguous tensor holding x's elements, whether x is its transpose)."""
-    if x.stride(-1) == 1:
-        return x, False
-    if x.dim() == 2 and x.stride(0) == 1:
-        return x.t(), True
-    return x.contiguous(), False
-
-
-def gemm(out: torch.Tensor, a: torch.Tensor, b: torch.Tensor, beta: float = 0.0,
-         bias: Optional[torch.Tensor] = None, bt: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """out = beta * out + a . b (+ bias[N]): bf16 operands, fp32 accumulate, fp32 or bf16 ``out``
-    written in place (row slices of bigger buffers included).  Transposed views of stored
-    operands are passed as (storage, transpose flag), never copied.  ``bt``: a row-major [N][K]
-    twin of ``b`` (a packed weight layout) -- with it, or when ``b`` is itself the transpose of a
-    row-major [N][K] matrix, the hand-written MFMA GEMM is eligible (TSAMD_GEMM_BT)."""
-    if BLT and out.is_cuda and a.dtype == BF and b.dtype == BF:
-        sa, ta = _stored(a)
-        sb, tb = _stored(b)
-        Bt = sb if tb else bt
-        if _use_bt(out, sa, ta, Bt, beta, bias, sb, tb):
-            _ops().gemm_bt(sa, Bt, out, float(beta), bias, None, None, 0, 0, 0, None)
-            return out
-        _ops().blt_mm(sa, sb, out, ta, tb, float(beta), bias)
-        return out
-    if beta != 0.0:
-        assert bias is None
-        if out.dtype == F32 and a.dtype == BF:
-            return torch.addmm(out, a, b, out_dtype=F32, out=out)
-        return out.addmm_(a, b, beta=beta)
-    if out.dtype == F32 and a.dtype == BF:
-        if bias is None:
-            return torch.mm(a, b, out_dtype=F32, out=out)
-        return torch.addmm(bias, a, b, out_dtype=F32, out=out)
-    if bias is None:
-        return torch.mm(a, b, out=out)
-    return torch.addmm(bias.to(out.dtype), a, b, out=out)
-
-
-def mm_into(out: torch.Tensor, a: torch.Tensor, b: torch.Tensor, bias: Optional[torch.Tensor] = None,
-            bt: Optional[torch.Tensor] = None):
-    """out = a . b (+ bias), fp32 accumulate, written straight into ``out`` (fp32 or bf16)
-    -- no temporary, no separate bias pass (GEMM bias epilogue)."""
-    return gemm(out, a, b, 0.0, bias, bt)
-
-
-def wgrad_into(out: torch.Tensor, a: torch.Tensor, b: torch.Tensor):
-    """out[M,N] = a[K,M]^T . b[K,N] for weight gradients: K (= rows: tokens or decoder steps
-    x batch) is long and M x N is a handful of output tiles.  blt_mm picks among hipBLASLt's
-    stream-K / split-K solutions per shape.  The torch path (TSAMD_BLT=0) splits K into S
-    chunks as one batched GEMM (S x the tiles, fp32 partials) and sums the partials: 3-5x
-    faster than torch.mm's pick for K = 25.6k-102k (tools/wgrad_micro.py)."""
-    K = a.shape[0]
-    if a.is_cuda and BLT_WGRAD and a.dtype == BF:
-        return gemm(out, a.t(), b)
-    if a.is_cuda:
-        for S in ((32, 16, 8) if K >= 65536 else (16, 8)):
-            if K % S == 0 and K // S >= 256:
-                parts = torch.bmm(a.reshape(S, K // S, a.shape[1]).transpose(1, 2), b.reshape(S, K // S, b.shape[1]),
-                                  out_dtype=F32)
-                return torch.sum(parts, 0, out=out)
-    return out.copy_(mmf(a.t(), b))
-
-
-WGRAD_TT = os.environ.get("TSAMD_WGRAD_TT", "1") != "0"
-WGRAD_TT_MIN = float(os.environ.get("TSAMD_WGRAD_TT_MIN", 1e11))
-_WG_WS: Dict[object, torch.Tensor] = {}
-_WG_WS_OLD: List[torch.Tensor] = []
-
-
-def wgrad_enc_into(out: torch.Tensor, a: torch.Tensor, b: torch.Tensor):
-    """Long-K weight gradients out = a^T . b: the encoder's x^T.dz / h^T.dz (K = T.B tokens:
-    102k at the headline, 1.6M at config #5) and the inline decoder-side ones (K = D.B): the
-    hand-written deterministic split-K GEMM (wgrad.hip ``wgrad_tt``: fp32 slabs summed in split
-    order, no atomics, no torch.sum pass) where the shape fits it and is large, else
-    ``wgrad_into``.  Its slab workspace is one buffer per device, grown outside graph capture
-    (the trainer's eager warm-up) and reused by the captured graphs: these calls run one after
-    another on the backward stream (model.py:290-297 / 89-93 gradients)."""
-    # large shapes only (config #5: K.M.N >= 3e11); at the headline's K = 102k the split-K bmm is
-    # as fast or faster (profiles/r6/wgrad_tt.md)
-    if (WGRAD_TT and a.is_cuda and a.dtype == BF and b.dtype == BF and out.dtype == F32
-            and a.shape[0] * a.shape[1] * b.shape[1] >= WGRAD_TT_MIN):
-        k = _ops()
-        n = int(k.wgrad_tt_ws(a.shape[1], b.shape[1], a.shape[0]))
-        if n > 0:
-            key = out.device
-            ws = _WG_WS.get(key)
-            if ws is None or ws.numel() < n:
-                if torch.cuda.is_current_stream_capturing():
-                    return wgrad_into(out, a, b)  # first seen inside a capture: no allocation there
-                if ws is not None:  # graphs captured earlier may hold the old buffer: never freed
-                    _WG_WS_OLD.append(ws)
-                ws = _WG_WS[key] = torch.empty(n, device=out.device, dtype=F32)
-            if k.wgrad_tt(a, b, out, ws, False):
-                return out
-    return wgrad_into(out, a, b)
-
-
-def mmf(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-    """bf16 x bf16 -> fp32 GEMM (fp32 accumulate), hipBLASLt."""
-    if BLT and a.is_cuda:
-        return gemm(torch.empty(a.shape[0], b.shape[1], device=a.device, dtype=F32), a, b)
-    if not a.is_cuda:  # (the out_dtype matmul is GPU-only)
-        return a.float() @ b.float()
-    return torch.mm(a, b, out_dtype=F32)
-
-
-def host_inputs(batch, hps, D: int, sort_rows: bool = False, need_grad: bool = True) -> Dict[str, np.ndarray]:
-    """The engine's per-batch inputs as host arrays (pure numpy: runs in loader worker
-    processes too): token ids, lengths, the reversed-index map of the backward LSTM
-    direction, extended-vocab ids, step-major decoder inputs / targets and the per-(step,
-    row) loss weights of the reference's loss averaging (``model.py:252-268``).
-
-    ``sort_rows``: the engine's rows are the batch's rows ordered by live decoder steps, longest
-    first (stable), so the steps a row skips past its summary form a suffix of the rows at every
-    decoder step and whole 16-row tiles of the decoder kernels go idle together.  The loss is a
-    sum over rows; ``row_src[b]`` is the batch row of engine row b.
-
-    ``need_grad`` False (decode / eval packs): the embedding-gradient id order is not computed
-    (zeros; no backward reads it) -- the largest host cost of a serving batch."""
-    T = batch.enc_batch.shape[1]
-    lens = batch.enc_lens.astype(np.int64)
-    if lens.min() < 1:
-        raise ValueError("empty article in batch")
-    t = np.arange(T)[None, :]
-    rev = np.where(t < lens[:, None], lens[:, None] - 1 - t, t)
-    valid = batch.valid.astype(np.float64)
-    nvalid = valid.sum()
-    if batch.dec_batch.shape[1] < D:
-        raise ValueError(f"batch has {batch.dec_batch.shape[1]} decoder steps, engine needs {D}")
-    dm = batch.dec_padding_mask[:, :D].astype(np.float64)
-    dec_lens = dm.sum(1)
-    if hps.pointer_gen:
-        rowg = dm * (valid / (np.maximum(dec_lens, 1) * nvalid))[:, None]
-    else:  # sequence_loss: sum(mask*CE)/sum(mask)
-        wm = dm * valid[:, None]
-        rowg = wm / wm.sum()
-    gcl = hps.cov_loss_wt * dm * (valid / (np.maximum(dec_lens, 1) * nvalid))[:, None]
-    # live decoder steps per row: 1 + the last step with a nonzero loss weight (0: none).  Steps
-    # past it reach only masked loss terms (model.py:252-268), so their forward values and
-    # gradients need not be computed (EngineConfig.skip_pad_steps)
-    live = (rowg != 0) | (gcl != 0)  # [B, D]
-    dlen = np.where(live.any(1), D - np.argmax(live[:, ::-1], 1), 0)
-    src = np.argsort(-dlen, kind="stable") if sort_rows else np.arange(len(dlen))
-    enc_batch, ext, rev = batch.enc_batch[src], batch.enc_batch_extend_vocab[src], rev[src]
-    enc_lens, rowg, gcl, dlen = batch.enc_lens[src], rowg[src], gcl[src], dlen[src]
-    dec_t = np.ascontiguousarray(batch.dec_batch[src, :D].T).astype(np.int64)
-    if need_grad:
-        sid, perm = emb_sort(enc_batch, dec_t)
-    else:
-        sid = perm = np.zeros(enc_batch.size + dec_t.size, dtype=np.int32)
-    # the fused vocab head's 32-row blocks of the t-major [D * B] rows that hold a live row, listed
-    # first (vblk, vblk_n of them); vlive per block (the blocks pass 2 must keep zeroed)
-    nb = (D * len(dlen) + 31) // 32
-    lr = np.zeros(nb * 32, dtype=bool)
-    lr[:D * len(dlen)] = (np.arange(D)[:, None] < dlen[None, :]).reshape(-1)
-    vlive = lr.reshape(nb, 32).any(1)
-    vblk = np.full(nb, nb, dtype=np.int32)  # past vblk_n: the dummy (all-zero) block nb of the compacted head
-    live_ids = np.nonzero(vlive)[0]
-    vblk[:len(live_ids)] = live_ids
-    return {
-        "enc_batch": enc_batch.astype(np.int64),
-        "enc_lens": enc_lens.astype(np.int32),
-        "rev_idx": rev.astype(np.int64),
-        "ext": ext.astype(np.int32),
-        "dec_batch_t": dec_t,
-        "target_t": np.ascontiguousarray(batch.target_batch[src, :D].T).astype(np.int32),
-        "rowg": np.ascontiguousarray(rowg.T).astype(np.float32),
-        "gcl": np.ascontiguousarray(gcl.T).astype(np.float32),
-        "emb_sid": sid,
-        "emb_perm": perm,
-        "dlen": dlen.astype(np.int32),
-        "row_src": src.astype(np.int32),
-        "vlive": vlive.astype(np.int32),
-        "vblk": vblk,
-        "vblk_n": np.array([len(live_ids)], dtype=np.int32),
-    }
-
-
-def emb_sort(enc_batch: np.ndarray, dec_t: np.ndarray):
-    """Stable id order of the step's embedding-gradient rows: the encoder tokens (row b*T + t)
-    then the decoder inputs (row B*T + t*B + b).  Returns (sorted ids, row permutation), int32.
-
-    Computed on the host with the batch (a loader worker process when one is used) instead of
-    a device sort inside the captured backward: torch.sort of more than ~1M keys (rocprim's
-    onesweep radix sort) faulted the GPU on the second replay of the captured graph at config #5
-    batch 2048 (memory-aperture violation at that kernel, three runs; the same step eager and
-    kernel-serialised ran clean: profiles/r3/b2048_fault.md).  The stable order also makes the
-    gradient's per-id summation order a function of the batch alone (deterministic mode)."""
-    ids = np.concatenate([np.asarray(enc_batch).reshape(-1), np.asarray(dec_t).reshape(-1)])
-    if ids.size and (ids.min() < 0 or ids.max() >= 2 ** 31):
-        raise ValueError("token ids out of range")
-    # numpy's stable sort is a radix sort for 16-bit keys: ~5 ms for 230k ids, 28 ms for 1.8M
-    key = ids.astype(np.uint16) if ids.size == 0 or ids.max() < 65536 else ids.astype(np.int32)
-    perm = np.argsort(key, kind="stable").astype(np.int32)
-    return ids[perm].astype(np.int32), perm
-
-
-_NP = {torch.long: np.int64, torch.int32: np.int32, F32: np.float32}
-
-
-def input_layout(B: int, T: int, D: int):
-    """Byte layout of the engine's input pack: [(name, offset, shape, torch dtype, nbytes)],
-    total size (every array 256-byte aligned); the device copy is one buffer with views."""
-    shapes = {"BT": (B, T), "B": (B,), "DB": (D, B), "R": (B * T + D * B,), "VB": ((D * B + 31) // 32,), "1": (1,)}
-    layout, off = [], 0
-    for name, sk, dt in (("enc_batch", "BT", torch.long), ("enc_lens", "B", torch.int32),
-                         ("rev_idx", "BT", torch.long), ("ext", "BT", torch.int32),
-                         ("dec_batch_t", "DB", torch.long), ("target_t", "DB", torch.int32),
-                         ("rowg", "DB", F32), ("gcl", "DB", F32),
-                         ("emb_sid", "R", torch.int32), ("emb_perm", "R", torch.int32), ("dlen", "B", torch.int32),
-                         ("row_src", "B", torch.int32), ("vlive", "VB", torch.int32), ("vblk", "VB", torch.int32),
-                         ("vblk_n", "1", torch.int32)):
-        shp = shapes[sk]
-        nb = int(np.prod(shp)) * np.dtype(_NP[dt]).itemsize
-        layout.append((name, off, shp, dt, nb))
-        off += (nb + 255) // 256 * 256
-    return layout, off
-
-
-def pack_host_inputs(host: Dict[str, np.ndarray], layout, out: Optional[np.ndarray] = None) -> np.ndarray:
-    """host_inputs arrays -> one uint8 buffer in ``layout`` order (``out`` if given)."""
-    if out is None:
-        out = np.zeros(layout[-1][1] + (layout[-1][4] + 255) // 256 * 256, dtype=np.uint8)
-    for name, o, shp, dt, nb in layout:
-        a = np.ascontiguousarray(host[name], dtype=_NP[dt])
-        if a.shape != tuple(shp):
-            raise ValueError(f"input {name}: shape {a.shape} != {tuple(shp)}")
-        out[o:o + nb] = a.reshape(-1).view(np.uint8)
-    return out
 
 
 def pack_job_rows(pairs, max_jobs: Optional[int] = None):
@@ -491,11 +127,12 @@ class HipPointerGenerator:
         if B * T >= 2 ** 31 or self.D * B * max(self.V, 4 * self.H) >= 2 ** 62:
             raise ValueError(f"batch {B} x enc {T} exceeds the kernels' 32-bit row counts")
         self.k = _ops()
+        self.blt_vdw = gemm_dispatch.BLT and cfg.blt_vocab_dw  # the vocab dW through blt_mm (default: split-K bmm)
         self.grad_scale = 1.0  # set to 1/world by a data-parallel trainer (see optimizer_step)
         # set by a data-parallel trainer: a persistent-LSTM timeout poisons the last gradient
         # element before its bucket's all-reduce, so every rank skips that update (poison_where)
         self.poison_on_lstm_err = False
-        self.split_vocab_dw = False  # see _dw_job (the graph trainer sets it with TSAMD_VOCAB_DW_SIDE)
+        self.split_vocab_dw = False  # see _dw_job (the graph trainer sets it with cfg.vocab_dw_side)
         self.dec_force_chains = set()  # "fwd" / "bwd": run that loop as chains although it is eligible (tools)
         self._dec_xbuf = self._dec_bwd_xbuf = None
         self.nchunk = int(self.k.attn_chunks(T))
@@ -557,10 +194,11 @@ class HipPointerGenerator:
         self._copy_stream = torch.cuda.Stream(self.dev)
         self._in_i = 0
         # upper encoder layers' input gradients through the merged hand-written GEMM (no dxs)
-        self.dx_merge = (DX_MERGE and L > 1 and BLT and GEMM_BT != "0" and self.dev.type == "cuda"
+        self.dx_merge = (self.cfg.dx_merge and L > 1 and gemm_dispatch.BLT and gemm_dispatch.GEMM_BT != "0"
+                         and self.dev.type == "cuda"
                          and hasattr(self.k, "gemm_bt_merge") and bool(self.k.gemm_bt_ok(T * B, H, 8 * H)))
         # layer 0's input projection inside the persistent recurrence (no gx)
-        self.lstm_fx = (LSTM_FX and self.cfg.persistent_lstm and self.dev.type == "cuda"
+        self.lstm_fx = (self.cfg.lstm_fx and self.cfg.persistent_lstm and self.dev.type == "cuda"
                         and hasattr(self.k, "lstm_persistent_fx_ok") and bool(self.k.lstm_persistent_fx_ok(H, B, E)))
         # encoder, per layer
         self.enc = []
@@ -689,9 +327,9 @@ class HipPointerGenerator:
                 w[n] = z(N)
             w["dbias"] = z(V)  # output_projection/v gradient, column sums taken inside pass 2
             w["vstate"] = z((N + 31) // 32, dt=torch.int32)  # dlogits blocks written by the last pass 2
-        # the fused head's dlogits rows: Vp columns (TSAMD_VOCAB_PAD; the columns past V stay zero)
-        self.Vp = -(-V // 128) * 128 if (self.fused_vocab and VOCAB_PAD) else V
-        self.ctx_native = CTX_NATIVE and self.dev.type == "cuda" and bool(self.k.ctx_bmm_ok(B, T, D, A))
+        # the fused head's dlogits rows: Vp columns (cfg.vocab_pad; the columns past V stay zero)
+        self.Vp = -(-V // 128) * 128 if (self.fused_vocab and cfg.vocab_pad) else V
+        self.ctx_native = cfg.ctx_native and self.dev.type == "cuda" and bool(self.k.ctx_bmm_ok(B, T, D, A))
         w["logits"] = z(D * B, self.Vp, dt=BF)
         if self.Vp != V and self.det:
             w["dbias_p"] = z(self.Vp)  # deterministic column sums over the padded rows
@@ -720,7 +358,7 @@ class HipPointerGenerator:
         w["dF"] = z(B, T, A, dt=BF)  # written whole (zeros past len) by attn_bwd_feat, in bf16
         w["ATTb"] = z(D, B, T, dt=BF)
         w["DCTXb"] = z(D, B, A, dt=BF)
-        self.de_bf16 = DE_BF16 and self.ctx_native and self.persistent_lstm
+        self.de_bf16 = cfg.de_bf16 and self.ctx_native and self.persistent_lstm
         self._dE = z(B, T, A, dt=BF if self.de_bf16 else F32)
         self._pending_dw = None
         # attn_bwd_feat partial rows (spread the atomics), summed after; deterministic mode: one
@@ -955,7 +593,7 @@ class HipPointerGenerator:
     # ------------------------------------------------------------------ forward
     def _frame_gemm_bt(self, layer: int) -> bool:
         """The input projection of encoder layer ``layer`` through the hand-written gather GEMM
-        (its A rows read through the step frame: no to_step_frame pass) -- by TSAMD_GEMM_BT, timed
+        (its A rows read through the step frame: no to_step_frame pass) -- by gemm_dispatch.GEMM_BT, timed
         once per shape against the library GEMM alone (``FRAME_SLACK``: the gather path also saves
         the layout pass)."""
         st = self.enc[layer]
@@ -1255,7 +893,7 @@ class HipPointerGenerator:
             # elements: the library's strided-batched path is not trusted past 32-bit strides
             while Sw > 1 and (N // Sw) * V >= 2 ** 31 and N % (2 * Sw) == 0:
                 Sw *= 2
-            if not BLT_VDW and m == H and Sw > 1 and N % Sw == 0 and (N // Sw) * V < 2 ** 31:
+            if not self.blt_vdw and m == H and Sw > 1 and N % Sw == 0 and (N // Sw) * V < 2 ** 31:
                 # split K = N in Sw = 4 (one batched GEMM + a sum): 0.82 -> 0.74 ms at B = 256
                 xe = w["outb_ext"].view(Sw, N // Sw, H + 8)[:, :, :H]
                 parts = torch.bmm(xe.transpose(1, 2), dl.view(Sw, N // Sw, V), out_dtype=F32)
@@ -1297,7 +935,7 @@ class HipPointerGenerator:
         self._dout = de[:nb].view(nb * 32, H)[:N]
 
     def _vocab_grads_unpadded(self, dst, xc, dlc, H, V, M):
-        Sw = 4 if not BLT_VDW and M % 4 == 0 and (M // 4) * V < 2 ** 31 else 1
+        Sw = 4 if not self.blt_vdw and M % 4 == 0 and (M // 4) * V < 2 ** 31 else 1
         if Sw > 1:  # split K = M in 4 (one batched GEMM + a sum), as the full head
             parts = torch.bmm(xc.view(Sw, M // Sw, H + 8)[:, :, :H].transpose(1, 2), dlc.view(Sw, M // Sw, V),
                               out_dtype=F32)
@@ -1323,10 +961,10 @@ class HipPointerGenerator:
     def _vocab_dw(self, dst, x, dl):
         """dst[H][V] = x^T . dl[:, :V] (output-projection weight gradient, model.py:290-297 over
         model.py:229-236) from the padded dlogits rows dl [K][Vp]: the library GEMM at the aligned
-        N into a [H][Vp] scratch, then the first V columns; above VOCAB_DW_SPLIT_MIN the 4-way
+        N into a [H][Vp] scratch, then the first V columns; above cfg.vocab_dw_split_min the 4-way
         split-K batched GEMM (+ ordered torch.sum) as before."""
         K, H, V, Vp = dl.shape[0], self.H, self.V, self.Vp
-        if not BLT_VDW and K * H * V >= VOCAB_DW_SPLIT_MIN and K % 4 == 0 and (K // 4) * Vp < 2 ** 31:
+        if not self.blt_vdw and K * H * V >= self.cfg.vocab_dw_split_min and K % 4 == 0 and (K // 4) * Vp < 2 ** 31:
             parts = torch.bmm(x.unflatten(0, (4, K // 4)).transpose(1, 2), dl.view(4, K // 4, Vp), out_dtype=F32)
             torch.sum(parts[:, :, :V], 0, out=dst)
             return
@@ -1342,7 +980,7 @@ class HipPointerGenerator:
         K, H, Vp = dl.shape[0], self.H, self.Vp
         out = torch.empty(K, H, dtype=F32, device=self.dev)
         ow = self.pk["owP"]
-        if dl.is_cuda and GEMM_BT != "0":
+        if dl.is_cuda and gemm_dispatch.GEMM_BT != "0":
             k = self.k
             n = int(k.gemm_bt_splitk_ws(K, H, Vp))
             if n > 0:

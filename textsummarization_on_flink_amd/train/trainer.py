@@ -33,7 +33,7 @@ import torch
 
 from ..models.engine_config import fits_resident
 from ..models.params import FlatParams, build_params
-from ..models.pointer_generator import VOCAB_DW_SIDE, HipPointerGenerator, LstmHandoffError  # noqa: F401
+from ..models.pointer_generator import HipPointerGenerator, LstmHandoffError  # noqa: F401
 from ..parallel.dist import DistInfo, GradAllReducer, broadcast_params, rccl_cu_reserve
 from ..utils.graphs import capture_guard
 
@@ -126,9 +126,9 @@ class GraphTrainer:
         self.poison_next = False  # fault injection: NaN gradient on the next step (exercises the NaN guard)
         self.timing = False       # per-phase HIP-event timing (phase_ms)
         self._ev = None
-        # the vocab dW on a side stream beside the decoder backward loop (VOCAB_DW_SIDE): graph mode,
-        # padded fused vocab head only (the other heads compute dW and dX in one call)
-        self.dw_side = bool(use_graph and VOCAB_DW_SIDE and eng.fused_vocab and eng.Vp != eng.V)
+        # the vocab dW on a side stream beside the decoder backward loop (EngineConfig.vocab_dw_side): graph
+        # mode, padded fused vocab head only (the other heads compute dW and dX in one call)
+        self.dw_side = bool(use_graph and eng.cfg.vocab_dw_side and eng.fused_vocab and eng.Vp != eng.V)
         eng.split_vocab_dw = self.dw_side
         self.g_dw = {}
 

@@ -28,7 +28,7 @@ def timeit(fn, it=5):
 
 
 def main():
-    from textsummarization_on_flink_amd.models.pointer_generator import wgrad_into
+    from textsummarization_on_flink_amd.models.gemm_dispatch import wgrad_into
     from textsummarization_on_flink_amd.ops import ops
     k = ops()
     B, T, H = int(os.environ.get("B", "1024")), 800, 512

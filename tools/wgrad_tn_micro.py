@@ -1,5 +1,5 @@
 """The custom weight-gradient kernel (wgrad.hip: split-K MFMA, LDS transposed reads, fp32
-atomics, no inter-workgroup waits) vs the library split-K path (pointer_generator.wgrad_into)
+atomics, no inter-workgroup waits) vs the library split-K path (gemm_dispatch.wgrad_into)
 at the training step's weight-gradient shapes (B=256, D=100, T=400): error vs fp32 and
 HIP-event time per call.  Prints one JSON line per shape.
 
@@ -13,7 +13,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
-from textsummarization_on_flink_amd.models.pointer_generator import wgrad_into  # noqa: E402
+from textsummarization_on_flink_amd.models.gemm_dispatch import wgrad_into  # noqa: E402
 from textsummarization_on_flink_amd.ops import ops  # noqa: E402
 
 

@@ -1,6 +1,6 @@
 """The deterministic split-K weight-gradient GEMM (wgrad.hip wgrad_tt: 256 x 256 / 128 tiles,
 LDS-DMA staged K-major operands read by ds_read_b64_tr_b16, fp32 slabs summed in split order)
-vs the torch split-K path (pointer_generator.wgrad_into: bmm + torch.sum) and hipBLASLt (blt_mm)
+vs the torch split-K path (gemm_dispatch.wgrad_into: bmm + torch.sum) and hipBLASLt (blt_mm)
 at the encoder weight-gradient shapes: B = 256 (K = T.B = 102400) and config #5 at batch 2048
 (K = 800 x 2048 = 1638400).  Error vs fp32 and HIP-event time per call; one JSON line per shape.
 
@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
-from textsummarization_on_flink_amd.models import pointer_generator as pgm  # noqa: E402
+from textsummarization_on_flink_amd.models.gemm_dispatch import wgrad_into  # noqa: E402
 from textsummarization_on_flink_amd.ops import ops  # noqa: E402
 
 
@@ -47,13 +47,13 @@ def main():
         assert k.wgrad_tt(a, b, out, ws, False)
         err = float((out - ref).abs().max() / ref.abs().max())
         out2 = torch.empty(M, N, device="cuda")
-        pgm.wgrad_into(out2, a, b)
+        wgrad_into(out2, a, b)
         err_lib = float((out2 - ref).abs().max() / ref.abs().max())
         out3 = out.clone()
         k.wgrad_tt(a, b, out3, ws, False)
         flop = 2.0 * K * M * N
         t_tt = timed(lambda: k.wgrad_tt(a, b, out, ws, False))
-        t_lib = timed(lambda: pgm.wgrad_into(out2, a, b))
+        t_lib = timed(lambda: wgrad_into(out2, a, b))
         t_blt = timed(lambda: k.blt_mm(a, b, out2, True, False, 0.0, None))
         print(json.dumps({"shape": name, "K": K, "M": M, "N": N, "err": err, "err_split_k": err_lib,
                           "bitwise_repeat": bool(torch.equal(out, out3)), "ws_mb": round(ws.numel() * 4 / 2 ** 20, 1),
