@@ -1395,6 +1395,86 @@ void beam_gather(const Tensor& gidx, const Tensor& latest, const Tensor& c_src, 
                      A, T, E, V, unk, PO<int>(step), stream());
 }
 
+// ---------------------------------------------------------------- decode by sampling (sample.hip)
+// probe: out[r] = the Philox uniform of stream streams[r] at step step[0] (as it stands: no minus one)
+void sample_uniforms(int64_t seed, const Tensor& streams, const Tensor& step, const Tensor& out) {
+  chk(streams, at::kLong, "streams"); chk(step, I32, "step"); chk(out, F32, "out");
+  numel_eq(step, 1, "step"); numel_eq(out, streams.numel(), "out");
+  launch_sample_uniforms((unsigned long long)seed, P<long long>(streams), P<int>(step), P<float>(out),
+                         (int)streams.numel(), stream());
+}
+
+// The samples' bookkeeping in the tail of both draw kernels: all of done / tok_hist / lp_hist / lp_sum /
+// latest / slen, or none of them but (optionally) done; att / att_hist and pg / pg_hist in pairs.
+static SampleBook sample_book(const OT& done, const OT& tok_hist, const OT& lp_hist, const OT& lp_sum, const OT& latest,
+                              const OT& slen, const OT& att, const OT& att_hist, const OT& pg, const OT& pg_hist,
+                              int64_t R, int64_t T, int64_t max_dec) {
+  chko(done, I32, R, "done"); chko(tok_hist, I32, max_dec * R, "tok_hist"); chko(lp_hist, F32, max_dec * R, "lp_hist");
+  chko(lp_sum, F32, R, "lp_sum"); chko(latest, I32, R, "latest"); chko(slen, I32, R, "slen");
+  chko(att, F32, R * T, "att"); chko(att_hist, F32, max_dec * R * T, "att_hist");
+  chko(pg, F32, R, "pg"); chko(pg_hist, F32, max_dec * R, "pg_hist");
+  const bool book = PO<int>(tok_hist) != nullptr;
+  TORCH_CHECK(book == (PO<float>(lp_hist) != nullptr) && book == (PO<float>(lp_sum) != nullptr) &&
+                  book == (PO<int>(latest) != nullptr) && book == (PO<int>(slen) != nullptr) &&
+                  (!book || PO<int>(done)),
+              "sample bookkeeping: done, tok_hist, lp_hist, lp_sum, latest and slen together");
+  TORCH_CHECK((PO<float>(att) != nullptr) == (PO<float>(att_hist) != nullptr) &&
+                  (PO<float>(pg) != nullptr) == (PO<float>(pg_hist) != nullptr) &&
+                  (book || (!PO<float>(att_hist) && !PO<float>(pg_hist))),
+              "att / att_hist and pg / pg_hist come in pairs, with the bookkeeping");
+  return SampleBook{PO<int>(tok_hist), PO<float>(lp_hist), PO<float>(lp_sum), PO<int>(latest), PO<int>(slen),
+                    PO<int>(done), PO<float>(att), PO<float>(att_hist), PO<float>(pg), PO<float>(pg_hist)};
+}
+
+// top-k draw (k in 1..31) from the candidate lists [R][K], K >= k + 1; t = step[0] - 1
+void sample_topk(const Tensor& top_ids, const Tensor& top_lp, const Tensor& streams, const Tensor& step, int64_t seed,
+                 const Tensor& out_tok, const Tensor& out_lp, const Tensor& out_pick, int64_t R, int64_t K, int64_t k,
+                 double temp, int64_t stop_id, int64_t min_dec, int64_t max_dec, int64_t T, const OT& done,
+                 const OT& tok_hist, const OT& lp_hist, const OT& lp_sum, const OT& latest, const OT& slen,
+                 const OT& att, const OT& att_hist, const OT& pg, const OT& pg_hist) {
+  chk(top_ids, I32, "top_ids"); chk(top_lp, F32, "top_lp"); chk(streams, at::kLong, "streams"); chk(step, I32, "step");
+  chk(out_tok, I32, "out_tok"); chk(out_lp, F32, "out_lp"); chk(out_pick, I32, "out_pick");
+  TORCH_CHECK(R >= 1 && k >= 1 && k <= 31 && K >= k + 1 && K <= 32 && temp > 0 && max_dec >= 1 && T >= 1,
+              "bad sample_topk args (1 <= k <= 31, k + 1 <= K <= 32, temp > 0)");
+  numel_eq(top_ids, R * K, "top_ids"); numel_eq(top_lp, R * K, "top_lp"); numel_eq(streams, R, "streams");
+  numel_eq(step, 1, "step"); numel_eq(out_tok, R, "out_tok"); numel_eq(out_lp, R, "out_lp");
+  numel_eq(out_pick, R, "out_pick");
+  const SampleBook bk = sample_book(done, tok_hist, lp_hist, lp_sum, latest, slen, att, att_hist, pg, pg_hist, R, T,
+                                    max_dec);
+  launch_sample_topk(P<int>(top_ids), P<float>(top_lp), P<long long>(streams), P<int>(step), (unsigned long long)seed,
+                     P<int>(out_tok), P<float>(out_lp), P<int>(out_pick), (int)R, (int)K, (int)k, (float)temp,
+                     (int)stop_id, (int)min_dec, (int)max_dec, (int)T, bk, stream());
+}
+
+// draw from the whole extended-vocabulary mixture without scattering it; rows: rows per article.
+// err (optional, one int): set to 1 when a row has nothing to draw from (it then ends with [STOP], pick -1)
+void sample_full(const Tensor& logits, const Tensor& bias, const OT& pgen, const OT& attn, const Tensor& ext,
+                 const Tensor& lens, const Tensor& streams, const Tensor& step, int64_t seed, const Tensor& out_tok,
+                 const Tensor& out_lp, const Tensor& out_pick, int64_t R, int64_t V, int64_t T, int64_t rows,
+                 int64_t stop_id, int64_t min_dec, int64_t max_dec, const OT& done, const OT& tok_hist,
+                 const OT& lp_hist, const OT& lp_sum, const OT& latest, const OT& slen, const OT& att,
+                 const OT& att_hist, const OT& pg, const OT& pg_hist, const OT& err) {
+  chk(logits, F32, "logits"); chk(bias, F32, "bias"); chk(ext, I32, "ext"); chk(lens, I32, "lens");
+  chko(err, I32, 1, "err");
+  chk(streams, at::kLong, "streams"); chk(step, I32, "step"); chk(out_tok, I32, "out_tok"); chk(out_lp, F32, "out_lp");
+  chk(out_pick, I32, "out_pick");
+  TORCH_CHECK(R >= 1 && V >= 1 && T >= 1 && T <= 2048 && rows >= 1 && R % rows == 0 && max_dec >= 1,
+              "bad sample_full args (T <= 2048, rows | R)");
+  TORCH_CHECK((V + 255) / 256 + (T + 255) / 256 <= sample_full_max_chunks(), "vocab too large for sample_full");
+  numel_eq(logits, R * V, "logits"); numel_eq(bias, V, "bias"); numel_eq(ext, (R / rows) * T, "ext");
+  numel_eq(lens, R / rows, "lens"); numel_eq(streams, R, "streams"); numel_eq(step, 1, "step");
+  numel_eq(out_tok, R, "out_tok"); numel_eq(out_lp, R, "out_lp"); numel_eq(out_pick, R, "out_pick");
+  chko(pgen, F32, R, "pgen"); chko(attn, F32, R * T, "attn");
+  TORCH_CHECK((PO<float>(pgen) != nullptr) == (PO<float>(attn) != nullptr), "pgen and attn together (or neither)");
+  if (V % 4 == 0) { aligned(logits, 16, "logits"); aligned(bias, 16, "bias"); }
+  const SampleBook bk = sample_book(done, tok_hist, lp_hist, lp_sum, latest, slen, att, att_hist, pg, pg_hist, R, T,
+                                    max_dec);
+  launch_sample_full(P<float>(logits), P<float>(bias), PO<float>(pgen), PO<float>(attn), P<int>(ext), P<int>(lens),
+                     P<long long>(streams), P<int>(step), (unsigned long long)seed, P<int>(out_tok), P<float>(out_lp),
+                     P<int>(out_pick), (int)R, (int)V, (int)T, (int)rows, (int)stop_id, (int)min_dec, (int)max_dec,
+                     PO<int>(err), bk, stream());
+}
+
 void linear2(const Tensor& a1, int64_t K1, const OT& a2, int64_t K2, const Tensor& Wt, const OT& bias, const OT& add,
              const OT& out, const OT& outb, int64_t B, int64_t N) {
   chk(a1, BF, "a1"); chk(Wt, BF, "Wt");
@@ -1570,4 +1650,7 @@ TORCH_LIBRARY(tsamd, m) {
   m.def("beam_sproj_xmerge", &beam_sproj_xmerge);
   m.def("attn_fwd_row_beam", &attn_fwd_row_beam);
   m.def("pgen_bwd", &pgen_bwd);
+  m.def("sample_uniforms", &sample_uniforms);
+  m.def("sample_topk", &sample_topk);
+  m.def("sample_full", &sample_full);
 }

@@ -17,6 +17,7 @@
 #define CHK_BEAM_TOKEN 7   // beam gather: latest token id >= 0
 #define CHK_BEAM_SEQ 8     // n-gram blocking: token-sequence row in [0, R), position in [0, P), parent in [0, beam)
 #define CHK_BEAM_RANK 9    // wide beam bookkeeping: candidate rank in [0, candidates), result / hypothesis slot in [0, beam)
+#define CHK_SAMPLE_CHUNK 10  // full-distribution draw: the chunk that holds the crossing in [0, chunks)
 
 #ifdef TSAMD_DEBUG
 extern __device__ unsigned tsamd_dbg[4];

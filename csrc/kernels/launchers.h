@@ -141,6 +141,34 @@ void launch_beam_step_wide(const int* top_ids, const float* top_lp, float* lp_su
                            int* res_step, int* res_par, const int* step, const float* att, float* att_hist,
                            const float* pg, float* pg_hist, int T, int Na, int beam, int K, int stop_id, int min_dec,
                            int max_dec, hipStream_t st, const NgSeq* ng = nullptr, const BeamPen* pen = nullptr);
+// decode by sampling (sample.hip): the bookkeeping both draw kernels end in, per row that is not
+// done -- tok_hist == nullptr: the draw only
+struct SampleBook {
+  int* tok_hist;     // [max_dec][R]
+  float* lp_hist;    // [max_dec][R] the model's log-prob of the drawn token
+  float* lp_sum;     // [R]
+  int* latest;       // [R]
+  int* slen;         // [R] tokens drawn so far
+  int* done;         // [R] set when the row draws [STOP]; a done row is a no-op (read without tok_hist too)
+  const float* att;  // optional: [R][T] -> att_hist [max_dec][R][T]
+  float* att_hist;
+  const float* pg;   // optional: [R] -> pg_hist [max_dec][R]
+  float* pg_hist;
+};
+#define SAMPLE_FULL_MAX_CHUNKS 2304  // 256-entry chunks of V + T: V <= 524288, T <= 2048 and to spare
+int sample_full_max_chunks();
+void launch_sample_uniforms(unsigned long long seed, const long long* streams, const int* step, float* out, int R,
+                            hipStream_t st);
+void launch_sample_topk(const int* top_ids, const float* top_lp, const long long* streams, const int* step,
+                        unsigned long long seed, int* out_tok, float* out_lp, int* out_pick, int R, int K, int k,
+                        float temp, int stop_id, int min_dec, int max_dec, int T, const SampleBook& bk,
+                        hipStream_t st);
+// rows: rows per article (ext / lens are per article); pgen and attn both or neither (baseline);
+// err (optional, one word): set to 1 by a row that has nothing to draw from
+void launch_sample_full(const float* logits, const float* bias, const float* pgen, const float* attn, const int* ext,
+                        const int* lens, const long long* streams, const int* step, unsigned long long seed,
+                        int* out_tok, float* out_lp, int* out_pick, int R, int V, int T, int rows, int stop_id,
+                        int min_dec, int max_dec, int* err, const SampleBook& bk, hipStream_t st);
 void launch_beam_gather(const int* gidx, const int* latest, const float* c_src, const bf16* h_src,
                         const float* ctx_src, const float* a_src, const float* cov_src, const float* XGtab,
                         const float* Xtab, float* c_out, bf16* h_out, float* ctx_out, bf16* ctxb_out, float* cov_out,

@@ -82,9 +82,9 @@ def build_decoder(hps, vocab, batcher_factory, writer=None, device: Optional[str
     params, path, _ = load_params_for_decode(hps, vocab, device)
     ckpt_name = "ckpt-" + path.split("-")[-1] if hps.single_pass else None
     if device.startswith("cuda"):
-        from .decode.device_beam import DeviceBeamDecoder
+        from .decode.device_beam import device_decoder
         n = max(1, hps.decode_batch)
-        dev = DeviceBeamDecoder(hps, vocab, params, n_articles=n, T=hps.max_enc_steps, use_graph=hps.graph)
+        dev = device_decoder(hps, vocab, params, n_articles=n, T=hps.max_enc_steps, use_graph=hps.graph)
         batcher = batcher_factory(hps, n, hps.max_enc_steps)
 
         def reload():

@@ -75,6 +75,11 @@ class HParams:
     length_alpha: float = 0.9      # used by length_penalty = wu only
     coverage_penalty_beta: float = 0.0  # beam search: minus beta * sum_i max(coverage_i - 1, 0), the summary
                                         # penalty of Gehrmann et al. 2018 (needs coverage = 1; 0 = off)
+    sampling_topk: int = -1        # decode by sampling (decode/sampling.py): -1 = beam search, 0 = draw from the whole
+                                   # extended-vocabulary distribution, 1..31 = draw among the k most probable tokens
+    sampling_temp: float = 1.0     # top-k draws weigh a candidate by exp(log-prob / sampling_temp)
+    n_samples: int = 1             # independent samples per article (1..16); the most probable one is the summary
+    sample_seed: int = 0           # Philox key: the same seed gives the same samples whatever the batching
     stream_max_wait_ms: float = 0.0   # streaming decode: queued requests always share a batch; after
                                       # the first, wait at most this long for more (0 = no waiting)
     save_model_secs: int = 60      # Supervisor(save_model_secs=60), run_summarization.py:199
@@ -186,6 +191,32 @@ def check_penalties(hps) -> None:
                          "for coverage models")
 
 
+def sampling_on(hps) -> bool:
+    return int(getattr(hps, "sampling_topk", -1)) >= 0
+
+
+def check_sampling(hps) -> None:
+    """The decode-by-sampling options (host and device samplers refuse the same)."""
+    k = int(getattr(hps, "sampling_topk", -1))
+    if not -1 <= k <= 31:
+        raise ValueError("sampling_topk must be -1 (beam search), 0 (the whole distribution) or 1..31 (top-k)")
+    if not hps.sampling_temp > 0:
+        raise ValueError("sampling_temp must be > 0")
+    if not 1 <= hps.n_samples <= 16:
+        raise ValueError("n_samples must be in 1..16")
+    if not 0 <= hps.sample_seed < 2 ** 64:
+        raise ValueError("sample_seed must be in 0..2**64 - 1")
+    if k < 0:
+        return
+    if k == 0 and hps.sampling_temp != 1:
+        raise ValueError("sampling_topk = 0 draws from the model's distribution as it is: a temperature on the "
+                         "full pointer mixture is not defined here (sampling_temp must be 1)")
+    penalties = hps.length_penalty != "avg" or hps.coverage_penalty_beta > 0
+    if hps.block_ngram_repeat > 1 or penalties:
+        raise ValueError("sampling together with block_ngram_repeat or the length / coverage penalties is not "
+                         "built yet")
+
+
 def check_hps(hps: HParams) -> None:
     if hps.mode not in ("train", "eval", "decode"):
         raise ValueError("The 'mode' flag must be one of train/eval/decode")
@@ -197,6 +228,7 @@ def check_hps(hps: HParams) -> None:
     if hps.block_ngram_repeat < 0:
         raise ValueError("block_ngram_repeat must be >= 0 (0 or 1 = off)")
     check_penalties(hps)
+    check_sampling(hps)
 
 
 @dataclass

@@ -151,8 +151,7 @@ class OracleStepModel:
         return {"enc_out": enc_out, "F": F, "mask": mask, "ext": ext, "max_oovs": int(batch.max_art_oovs)}, \
             (c0[0], h0[0])
 
-    @torch.no_grad()
-    def decode_onestep(self, enc, latest_tokens, states, prev_coverage, k2):
+    def _step_inputs(self, enc, latest_tokens, states, prev_coverage):
         k = len(states)
         c = torch.stack([s[0] for s in states])
         h = torch.stack([s[1] for s in states])
@@ -160,14 +159,32 @@ class OracleStepModel:
         rep = lambda x: x.expand(k, *x.shape[1:])
         cov = torch.as_tensor(np.stack(prev_coverage), dtype=c.dtype, device=self.device) \
             if prev_coverage[0] is not None else None
-        ids, lp, c2, h2, a, pg, cov2 = self.ref.decode_onestep(
-            self.W, rep(enc["enc_out"]), rep(enc["F"]), rep(enc["mask"]), rep(enc["ext"]), enc["max_oovs"], tok, c, h,
-            cov, k2)
+        return k, rep, tok, c, h, cov
+
+    @staticmethod
+    def _step_outputs(k, c2, h2, a, pg, cov2):
         new_states = [(c2[i], h2[i]) for i in range(k)]
         attn = [a[i].cpu().numpy() for i in range(k)]
         pgens = [float(pg[i]) for i in range(k)] if pg is not None else [None] * k
         covs = [cov2[i].cpu().numpy() for i in range(k)] if cov2 is not None else [None] * k
-        return ids.cpu().numpy(), lp.cpu().numpy(), new_states, attn, pgens, covs
+        return new_states, attn, pgens, covs
+
+    @torch.no_grad()
+    def decode_onestep(self, enc, latest_tokens, states, prev_coverage, k2):
+        k, rep, tok, c, h, cov = self._step_inputs(enc, latest_tokens, states, prev_coverage)
+        ids, lp, c2, h2, a, pg, cov2 = self.ref.decode_onestep(
+            self.W, rep(enc["enc_out"]), rep(enc["F"]), rep(enc["mask"]), rep(enc["ext"]), enc["max_oovs"], tok, c, h,
+            cov, k2)
+        return (ids.cpu().numpy(), lp.cpu().numpy(), *self._step_outputs(k, c2, h2, a, pg, cov2))
+
+    @torch.no_grad()
+    def decode_onestep_parts(self, enc, latest_tokens, states, prev_coverage):
+        """``decode_onestep`` without the mixture and its top-k: the vocabulary softmax [k][V] in
+        place of (ids, log-probs) -- the parts the full-distribution draw (decode/sampling.py) reads."""
+        k, rep, tok, c, h, cov = self._step_inputs(enc, latest_tokens, states, prev_coverage)
+        vd, c2, h2, a, pg, cov2 = self.ref.decode_onestep_parts(
+            self.W, rep(enc["enc_out"]), rep(enc["F"]), rep(enc["mask"]), tok, c, h, cov)
+        return (vd.cpu().numpy(), *self._step_outputs(k, c2, h2, a, pg, cov2))
 
 
 def run_beam_search(model, vocab, batch, hps) -> Hypothesis:

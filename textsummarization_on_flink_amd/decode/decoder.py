@@ -23,9 +23,11 @@ import shutil
 import time
 from typing import List, Optional
 
+from ..config import sampling_on
 from ..data import vocab as V
 from . import rouge
 from .beam_search import run_beam_search
+from .sampling import best_sample, run_sampling
 
 log = logging.getLogger(__name__)
 SECS_UNTIL_NEW_CKPT = 60
@@ -80,6 +82,8 @@ def get_decode_dir_name(hps, ckpt_name: Optional[str]) -> str:
         raise ValueError("FLAGS.data_path %s should contain one of train, val or test" % dp)
     name = "decode_%s_%imaxenc_%ibeam_%imindec_%imaxdec" % (dataset, hps.max_enc_steps, hps.beam_size,
                                                              hps.min_dec_steps, hps.max_dec_steps)
+    if sampling_on(hps):
+        name += "_sample%i" % hps.sampling_topk
     if ckpt_name is not None:
         name += "_%s" % ckpt_name
     return name
@@ -151,7 +155,12 @@ class BeamSearchDecoder:
         return words
 
     def decode_one_batch(self, batch, mode="auto"):
-        best = run_beam_search(self.model, self.vocab, batch, self.hps)
+        if sampling_on(self.hps):
+            # sample-and-rank; article g of the run draws from streams g * n_samples ..
+            best = best_sample(run_sampling(self.model, self.vocab, batch, self.hps,
+                                            sample_base=self.hps.n_samples * self.counter))
+        else:
+            best = run_beam_search(self.model, self.vocab, batch, self.hps)
         return self.handle(best, batch, 0, mode)
 
     # ------------------------------------------------------------------ loops

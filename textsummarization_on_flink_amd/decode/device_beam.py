@@ -35,8 +35,9 @@ from ..models.pointer_generator import (ATT_B, CELL_B, CELL_K, EMB, LIN_B, LIN_M
 from ..models.engine_config import EngineConfig
 from ..models.gemm_dispatch import mmf
 from ..utils.graphs import capture_guard
-from ..config import check_penalties
+from ..config import check_penalties, check_sampling, sampling_on
 from .beam_search import Hypothesis, inv_len_table, penalties_on
+from .sampling import best_sample
 
 BF = torch.bfloat16
 F32 = torch.float32
@@ -46,6 +47,7 @@ class DeviceBeamDecoder:
     pen = None  # length / coverage penalties off unless __init__ finds them in hps
 
     MAX_BEAM = 16  # beam * 2 beam candidates per article: what the wide bookkeeping kernel ranks
+    _width_name = "beam_size"  # the flag ``_width`` reads
 
     def __init__(self, hps, vocab, params, n_articles: int, T: int, use_graph: bool = True, chunk: int = 10,
                  keep_attn: bool = True, wide_beam: bool = False):
@@ -53,11 +55,12 @@ class DeviceBeamDecoder:
         the 32-entry list, workgroup-wide bookkeeping) at any beam size (a test switch: the narrow
         kernels are the faster ones where they apply).  Beam sizes above 5 always take the wide
         bookkeeping, by default behind the fused vocab head."""
-        if hps.beam_size > self.MAX_BEAM:
-            raise ValueError(f"beam_size {hps.beam_size} exceeds {self.MAX_BEAM}, the largest beam the device "
+        width = self._width(hps)
+        if width > self.MAX_BEAM:
+            raise ValueError(f"{self._width_name} {width} exceeds {self.MAX_BEAM}, the largest beam the device "
                              "decoder runs (the host beam search takes any size)")
         self.hps, self.vocab, self.p = hps, vocab, params
-        self.Na, self.beam = n_articles, hps.beam_size
+        self.Na, self.beam = n_articles, width
         self.R = self.Na * self.beam
         # beams 1..5 (up to 64 candidates per article) run the one-wave bookkeeping and, where the
         # shape allows, the fused select with the bookkeeping in its tail; 6..16 the unfused step with
@@ -68,7 +71,7 @@ class DeviceBeamDecoder:
         # sizes fall back to replicating E/F per hypothesis (wide beams with the row kernel:
         # rep = beam, set below once the attention variant is known)
         self.rep = self.beam if self.beam in (1, 2, 4) else 1
-        self.K = 2 * self.beam
+        self.K = self._candidates()
         self.T = T
         self.V = vocab.size()
         self.maxD = hps.max_dec_steps
@@ -123,6 +126,15 @@ class DeviceBeamDecoder:
         self._captured_now = False
 
     # ------------------------------------------------------------------ setup
+    @staticmethod
+    def _width(hps) -> int:
+        """Rows per article (``DeviceSampler``: the samples take the place of the beam)."""
+        return hps.beam_size
+
+    def _candidates(self) -> int:
+        """Entries per row of the step's candidate lists."""
+        return 2 * self.beam
+
     def _alloc(self):
         R, T, H, A, E, V, K, Na, D = self.R, self.T, self.eng.H, self.eng.A, self.eng.E, self.V, self.K, self.Na, \
             self.maxD
@@ -342,6 +354,13 @@ class DeviceBeamDecoder:
         if hps.pointer_gen and not self.fused_vocab:
             k.pgen(Y["CTX"], Y["C"], Y["H"], b["x"], self.pg_w, p[PG_B], b["PG"], R, A, H, E)
         k.linear2(Y["H"], H, b["ctx_bf"], A, eng.pk["OUTmT"], p[OUT_B], None, None, b["outb"], R, H)
+        self._select(Y, pg)
+        self._book(Y, pg)
+
+    def _select(self, Y, pg):
+        """The vocab head of the unfused step: this step's candidate lists top_ids / top_lp."""
+        k, b, hps, eng, p = self.k, self.b, self.hps, self.eng, self.p
+        R, T, H, A, E, V, K = self.R, self.T, eng.H, eng.A, eng.E, self.V, self.K
         if self.fused_vocab and hps.pointer_gen:
             # p_gen is computed inside the select kernel (into b["PG"] for the histories)
             k.vocab_topk_pg(b["outb"], self.owT, p[OV], Y["CTX"], Y["C"], Y["H"], b["x"], self.pg_w, p[PG_B], b["PG"],
@@ -355,8 +374,12 @@ class DeviceBeamDecoder:
             topk = k.final_topk_wide if self.wide else k.final_topk
             topk(b["logits"], p[OV], pg, Y["ATT"] if hps.pointer_gen else None, b["ext"], b["lens"],
                  b["top_ids"], b["top_lp"], b["part_ms"], b["part_v"], b["part_i"], R, V, T, K, self.beam)
-        # beam bookkeeping; also appends a_t / p_gen to the histories (b["step"] was advanced by
-        # this step's beam_gather: no grid-wide counter here)
+
+    def _book(self, Y, pg):
+        """Beam bookkeeping of the unfused step; also appends a_t / p_gen to the histories
+        (b["step"] was advanced by this step's beam_gather: no grid-wide counter here)."""
+        k, b, hps = self.k, self.b, self.hps
+        T, K = self.T, self.K
         hist = self.keep_attn
         args = (b["top_ids"], b["top_lp"], b["lp_sum"], b["latest"], b["gidx"], b["tok_hist"], b["par_hist"],
                 b["done"], b["res_count"], b["res_score"], b["res_len"], b["res_step"], b["res_par"], b["step"],
@@ -796,3 +819,156 @@ class DeviceBeamDecoder:
         self.eng.check_lstm_err()  # the encoder ran the persistent LSTM: never emit garbage summaries
         self._check_tail(int(self.b["tail_err"].item()))
         return hyps
+
+
+class DeviceSampler(DeviceBeamDecoder):
+    """Decode by sampling on the device (``decode.sampling`` holds the rule): ``n_articles x
+    n_samples`` rows, every row an independent sample of its article with its own Philox stream.
+
+    The decode step is the parent's unfused one up to the candidate lists -- ``n_samples`` takes the
+    place of the beam in ``rep``, in the selects and in the encoder-state replication -- and ends in
+    ``sample_topk`` (k in 1..31, behind the vocab head with k + 1 candidates) or, for k = 0, in
+    ``sample_full`` behind the materialised head (library GEMM into the logits buffer, ``pgen``).
+    The draw kernels' tail keeps the samples' books (token / log-prob histories, done flag and
+    length per row, identity parents), so early exit, graph capture in chunks, the snapshot
+    pipelining and the LSTM error check are the parent's.
+
+    ``sample(batch, sample_base)`` returns every sample; ``decode`` / ``decode_batches`` yield
+    ``best_sample`` per article and count the articles decoded so far for the stream ids."""
+
+    def __init__(self, hps, vocab, params, n_articles: int, T: int, use_graph: bool = True, chunk: int = 10,
+                 keep_attn: bool = True):
+        check_sampling(hps)
+        if not sampling_on(hps):
+            raise ValueError("DeviceSampler needs sampling_topk >= 0 (DeviceBeamDecoder runs beam search)")
+        self.topk, self.n_samples = int(hps.sampling_topk), int(hps.n_samples)
+        self.articles_seen = 0  # decode / decode_batches: sample_base = n_samples * articles decoded so far
+        super().__init__(hps, vocab, params, n_articles, T, use_graph=use_graph, chunk=chunk, keep_attn=keep_attn)
+
+    _width_name = "n_samples"
+
+    @staticmethod
+    def _width(hps) -> int:
+        return int(hps.n_samples)
+
+    @staticmethod
+    def _check_tail(err: int) -> None:
+        if err:
+            raise RuntimeError("sampling decode: a row had nothing to draw from (every weight of its distribution "
+                               "was 0 or not a number); results discarded")
+
+    def _candidates(self) -> int:
+        # the smallest list the selects take that holds the k + 1 best (k = 0 reads no list)
+        return self.topk + 1 if self.topk > 0 else 2
+
+    def _alloc(self):
+        super()._alloc()
+        self.fused_step = False  # the draw is the tail of the unfused step
+        R, D = self.R, self.maxD
+        z = lambda *s, dt=F32: torch.zeros(*s, dtype=dt, device=self.dev)  # noqa: E731
+        b = self.b
+        if self.topk == 0:
+            self.fused_vocab = False  # sample_full reads materialised logits and p_gen
+        else:
+            # the fused vocab head at every k: its select takes the 32-entry lists above 8 candidates at
+            # any number of rows per article (the parent keeps them for the wide beams, whose
+            # bookkeeping they feed)
+            self.fused_vocab = self.eng.cfg.fused_vocab_decode and (self.eng.H <= 256 or self.eng.H == 512)
+            if self.fused_vocab and "vpart_ms" not in b:
+                b["vpart_ms"] = z(R, int(self.k.vocab_topk_parts(self.V, self.eng.H)), 2)
+        b["done"] = z(R, dt=torch.int32)  # per sample (the parent's is per article)
+        b["lp_hist"], b["slen"] = z(D, R), z(R, dt=torch.int32)
+        b["streams"] = z(R, dt=torch.long)  # refilled per batch
+        b["s_tok"], b["s_lp"], b["s_pick"] = z(R, dt=torch.int32), z(R), z(R, dt=torch.int32)
+
+    def _prologue(self):
+        super()._prologue()
+        for n in ("lp_hist", "slen", "tail_err"):  # (tail_err: the draw's "nothing to draw from" word)
+            self.b[n].zero_()
+
+    def _book(self, Y, pg):
+        k, b, hps = self.k, self.b, self.hps
+        hist = self.keep_attn
+        seed = hps.sample_seed - (1 << 64) if hps.sample_seed >= (1 << 63) else hps.sample_seed  # as int64
+        stop = self.vocab.word2id(STOP_DECODING)
+        book = (b["done"], b["tok_hist"], b["lp_hist"], b["lp_sum"], b["latest"], b["slen"],
+                Y["ATT"] if hist else None, b["ATT_hist"] if hist else None,
+                pg if (hist and pg is not None) else None, b["PG_hist"] if (hist and pg is not None) else None)
+        if self.topk > 0:
+            k.sample_topk(b["top_ids"], b["top_lp"], b["streams"], b["step"], seed, b["s_tok"], b["s_lp"], b["s_pick"],
+                          self.R, self.K, self.topk, float(hps.sampling_temp), stop, hps.min_dec_steps, self.maxD,
+                          self.T, *book)
+        else:
+            k.sample_full(b["logits"], self.p[OV], pg, Y["ATT"] if pg is not None else None, b["ext"], b["lens"],
+                          b["streams"], b["step"], seed, b["s_tok"], b["s_lp"], b["s_pick"], self.R, self.V, self.T,
+                          self.beam, stop, hps.min_dec_steps, self.maxD, *book, b["tail_err"])
+
+    def _select(self, Y, pg):
+        if self.topk > 0:
+            return super()._select(Y, pg)
+        torch.mm(self.b["outb"], self.eng.pk["ow"], out_dtype=F32, out=self.b["logits"])
+
+    # ------------------------------------------------------------------ driver
+    def set_streams(self, sample_base) -> None:
+        """Row r = article a, sample s draws from stream sample_base + a * n_samples + s; a sequence
+        gives every article its own base (stream sample_base[a] + s)."""
+        n = self.n_samples
+        if isinstance(sample_base, (int, np.integer)):  # filled on the device: no host copy in the decode loops
+            torch.arange(int(sample_base), int(sample_base) + self.R, dtype=torch.long, device=self.dev,
+                         out=self.b["streams"])
+            return
+        ids = np.repeat(np.asarray(sample_base, np.int64), n) + np.tile(np.arange(n, dtype=np.int64), self.Na)
+        if ids.shape != (self.R,):
+            raise ValueError(f"sample_base: one base per article ({self.Na}) expected")
+        self.b["streams"].copy_(torch.from_numpy(ids))
+
+    def run_chunks(self, batch, pre_encoded: bool = False, next_batch=None, enc_src=None, sample_base=None):
+        base = self.n_samples * self.articles_seen if sample_base is None else sample_base
+        if sample_base is None:
+            self.articles_seen += self._n_valid(batch)
+        self.set_streams(base)
+        yield from super().run_chunks(batch, pre_encoded=pre_encoded, next_batch=next_batch, enc_src=enc_src)
+
+    def _result_names(self):
+        return ["tok_hist", "lp_hist", "slen"] + (["ATT_hist", "PG_hist"] if self.keep_attn else [])
+
+    def _samples(self, b, n_valid: int = None) -> List[List[Hypothesis]]:
+        n, start = self.n_samples, self.vocab.word2id(START_DECODING)
+        out = []
+        for a in range(n_valid if n_valid is not None else self.Na):
+            hyps = []
+            for r in range(a * n, (a + 1) * n):
+                L = int(b["slen"][r])
+                tokens = [start] + b["tok_hist"][:L, r].tolist()
+                lps = [0.0] + [float(x) for x in b["lp_hist"][:L, r]]
+                atts, pgs = [], []
+                if self.keep_attn:  # copies: b's arrays are views of pinned buffers that the next batch reuses
+                    atts = [b["ATT_hist"][t, r].copy() for t in range(L)]
+                    pgs = [float(b["PG_hist"][t, r]) if self.hps.pointer_gen else None for t in range(L)]
+                h = Hypothesis(tokens, lps, None, atts, pgs, None)
+                h.score = h.avg_log_prob
+                hyps.append(h)
+            out.append(hyps)
+        return out
+
+    def _backtrack(self, b, n_valid: int = None) -> List[Hypothesis]:
+        return [best_sample(hyps) for hyps in self._samples(b, n_valid)]
+
+    def _results_walk(self, n_valid: int = None) -> List[Hypothesis]:
+        return self.results(n_valid)
+
+    def sample(self, batch, sample_base: int = 0) -> List[List[Hypothesis]]:
+        """Every sample of every valid article of ``batch``: ``n_samples`` hypotheses each."""
+        self._rows_ok(batch)
+        for _ in self.run_chunks(batch, sample_base=sample_base):
+            pass
+        out = self._samples(self._fetch(self._result_names()), self._n_valid(batch))  # synchronises
+        self.eng.check_lstm_err()
+        self._check_tail(int(self.b["tail_err"].item()))
+        return out
+
+
+def device_decoder(hps, vocab, params, n_articles: int, T: int, **kw):
+    """The device decoder ``hps`` asks for: ``DeviceSampler`` with sampling on, else ``DeviceBeamDecoder``."""
+    cls = DeviceSampler if sampling_on(hps) else DeviceBeamDecoder
+    return cls(hps, vocab, params, n_articles=n_articles, T=T, **kw)

@@ -91,10 +91,10 @@ def _serve_packed(context, hps, vocab, pool):
     import time
     from textsummarization_on_flink_amd import cli
     from textsummarization_on_flink_amd.decode.decoder import SECS_UNTIL_NEW_CKPT
-    from textsummarization_on_flink_amd.decode.device_beam import DeviceBeamDecoder
+    from textsummarization_on_flink_amd.decode.device_beam import device_decoder
     params, _, _ = cli.load_params_for_decode(hps, vocab, "cuda")
-    dev = DeviceBeamDecoder(hps, vocab, params, n_articles=hps.decode_batch, T=hps.max_enc_steps,
-                            use_graph=hps.graph, keep_attn=False)
+    dev = device_decoder(hps, vocab, params, n_articles=hps.decode_batch, T=hps.max_enc_steps,
+                         use_graph=hps.graph, keep_attn=False)
     fifo = deque()
     t_load = time.time()
 

@@ -189,6 +189,18 @@ class ReferencePointerGenerator:
         """One beam step exactly as the decode graph (max_dec_steps=1,
         initial_state_attention=True).  Returns topk ids/log-probs (top 2*beam),
         new (c, h), attn, p_gen, coverage."""
+        vd, c, h, a, p_gen, cov = self.decode_onestep_parts(W, enc_out, F, mask, tokens, c, h, prev_cov)
+        if self.hps.pointer_gen:
+            fd = self.final_dist(vd, a, p_gen, ext_ids, max_oovs)
+        else:
+            fd = vd
+        probs, ids = torch.topk(fd, k2, dim=1)
+        return ids, torch.log(probs), c, h, a, p_gen, cov
+
+    def decode_onestep_parts(self, W, enc_out, F, mask, tokens, c, h, prev_cov):
+        """The decode step up to the parts of its output distribution: vocabulary softmax, new
+        (c, h), attn, p_gen, coverage (what the full-distribution draw of decode/sampling.py
+        reads; ``decode_onestep`` mixes them)."""
         hps = self.hps
         cov = prev_cov if hps.coverage else None
         ctx, _, cov = self.attention(W, enc_out, F, mask, c, h, cov)
@@ -198,12 +210,7 @@ class ReferencePointerGenerator:
         ctx, a, _ = self.attention(W, enc_out, F, mask, c, h, cov)
         p_gen, out = self.post_cell(W, ctx, c, h, x)
         vd = torch.softmax(self.vocab_logits(W, out), -1)
-        if hps.pointer_gen:
-            fd = self.final_dist(vd, a, p_gen, ext_ids, max_oovs)
-        else:
-            fd = vd
-        probs, ids = torch.topk(fd, k2, dim=1)
-        return ids, torch.log(probs), c, h, a, p_gen, cov
+        return vd, c, h, a, p_gen, cov
 
 
 def mask_and_avg(values, dec_mask, valid):
