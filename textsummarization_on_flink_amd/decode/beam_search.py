@@ -24,7 +24,8 @@ defaults (``avg``, beta 0) are the reference's rule and take the reference's pat
 
 The step model is pluggable (``StepModel``): the PyTorch oracle on CPU, or the gfx950
 decode step on GPU.  The batched device-resident version (many articles per launch,
-hipGraph-captured) lives in ``decode.device_beam``.
+hipGraph-captured) lives in ``decode.device_beam``, on the step trunk and batch pipeline of
+``decode.device_base`` that it shares with the sampler (``decode.device_sampler``).
 """
 from __future__ import annotations
 

@@ -11,8 +11,9 @@ Per example: beam search -> ids -> words (in-article OOVs restored) -> cut at th
 results are discarded); ``html_escape=True`` fixes it.
 
 Two engines plug in: the host beam search over a step model (CPU oracle, or any
-``StepModel``) and the batched device beam search (``decode.device_beam``), which decodes
-many articles per hipGraph replay and returns the same Hypothesis objects.
+``StepModel``) and the batched device decoder (``decode.device_beam.device_decoder``: the beam search
+of ``decode.device_beam`` or the sampler of ``decode.device_sampler``, both on ``decode.device_base``),
+which decodes many articles per hipGraph replay and returns the same Hypothesis objects.
 """
 from __future__ import annotations
 

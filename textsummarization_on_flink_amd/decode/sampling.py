@@ -5,7 +5,7 @@ token among the k most probable of the step's final (pointer-mixture) distributi
 whole extended-vocabulary distribution; ``hps.n_samples`` independent samples per article, each with
 its per-step model log-probs (what sample-and-rank decoding and self-critical training, Paulus et
 al. 2017, need).  This module defines the semantics; the device kernels (csrc/kernels/sample.hip,
-``decode.device_beam.DeviceSampler``) follow it, the arrangement of ``ngram_blocked`` / ``hyp_score``.
+``decode.device_sampler.DeviceSampler``) follow it, the arrangement of ``ngram_blocked`` / ``hyp_score``.
 
 Random numbers: Philox4x32-10 (Salmon et al. 2011), key (sample_seed & 0xffffffff, sample_seed >> 32),
 counter (t, stream & 0xffffffff, stream >> 32, 0) with t the decode step; the uniform is output word
