@@ -1475,6 +1475,24 @@ void sample_full(const Tensor& logits, const Tensor& bias, const OT& pgen, const
                      PO<int>(err), bk, stream());
 }
 
+// ---------------------------------------------------------------- ROUGE rewards (rouge.hip)
+// counts [R][5] = hit1, hit2, lcs, n_hyp, n_ref and reward [R] of the sampler's rows (tok_hist [D][R], slen [R])
+// against their article's reference (ref [R / rows][Lr], ref_len); kind 0 rouge_l, 1 rouge_1, 2 rouge_2, 3 mean
+void rouge_reward(const Tensor& tok_hist, const Tensor& slen, const Tensor& ref, const Tensor& ref_len,
+                  const Tensor& counts, const Tensor& reward, int64_t R, int64_t D, int64_t Lr, int64_t rows,
+                  int64_t stop_id, int64_t kind) {
+  chk(tok_hist, I32, "tok_hist"); chk(slen, I32, "slen"); chk(ref, I32, "ref"); chk(ref_len, I32, "ref_len");
+  chk(counts, I32, "counts"); chk(reward, F32, "reward");
+  TORCH_CHECK(D >= 1 && D <= ROUGE_MAX_LEN && Lr >= 1 && Lr <= ROUGE_MAX_LEN,
+              "rouge_reward: sequence lengths up to ", ROUGE_MAX_LEN, " (got D = ", D, ", Lr = ", Lr, ")");
+  TORCH_CHECK(R >= 1 && rows >= 1 && R % rows == 0 && kind >= 0 && kind <= 3,
+              "bad rouge_reward args (rows | R, kind in 0..3)");
+  numel_eq(tok_hist, D * R, "tok_hist"); numel_eq(slen, R, "slen"); numel_eq(ref, (R / rows) * Lr, "ref");
+  numel_eq(ref_len, R / rows, "ref_len"); numel_eq(counts, R * 5, "counts"); numel_eq(reward, R, "reward");
+  launch_rouge_reward(P<int>(tok_hist), P<int>(slen), P<int>(ref), P<int>(ref_len), P<int>(counts), P<float>(reward),
+                      (int)R, (int)D, (int)Lr, (int)rows, (int)stop_id, (int)kind, stream());
+}
+
 void linear2(const Tensor& a1, int64_t K1, const OT& a2, int64_t K2, const Tensor& Wt, const OT& bias, const OT& add,
              const OT& out, const OT& outb, int64_t B, int64_t N) {
   chk(a1, BF, "a1"); chk(Wt, BF, "Wt");
@@ -1653,4 +1671,5 @@ TORCH_LIBRARY(tsamd, m) {
   m.def("sample_uniforms", &sample_uniforms);
   m.def("sample_topk", &sample_topk);
   m.def("sample_full", &sample_full);
+  m.def("rouge_reward", &rouge_reward);
 }

@@ -18,6 +18,8 @@
 #define CHK_BEAM_SEQ 8     // n-gram blocking: token-sequence row in [0, R), position in [0, P), parent in [0, beam)
 #define CHK_BEAM_RANK 9    // wide beam bookkeeping: candidate rank in [0, candidates), result / hypothesis slot in [0, beam)
 #define CHK_SAMPLE_CHUNK 10  // full-distribution draw: the chunk that holds the crossing in [0, chunks)
+#define CHK_ROUGE_HYP_LEN 11  // rouge_reward: sample length in [0, min(D, 256)]
+#define CHK_ROUGE_REF_LEN 12  // rouge_reward: reference length in [0, min(Lr, 256)]
 
 #ifdef TSAMD_DEBUG
 extern __device__ unsigned tsamd_dbg[4];

@@ -169,6 +169,12 @@ void launch_sample_full(const float* logits, const float* bias, const float* pge
                         const int* lens, const long long* streams, const int* step, unsigned long long seed,
                         int* out_tok, float* out_lp, int* out_pick, int R, int V, int T, int rows, int stop_id,
                         int min_dec, int max_dec, int* err, const SampleBook& bk, hipStream_t st);
+// ROUGE rewards of self-critical fine-tuning (rouge.hip): one wave per hypothesis row over the sampler's
+// tok_hist [D][R] / slen [R] against ref [R / rows][Lr] / ref_len; counts [R][5] = hit1, hit2, lcs, n_hyp,
+// n_ref; kind 0 rouge_l, 1 rouge_1, 2 rouge_2, 3 their mean; D, Lr <= ROUGE_MAX_LEN
+#define ROUGE_MAX_LEN 256
+void launch_rouge_reward(const int* tok_hist, const int* slen, const int* ref, const int* ref_len, int* counts,
+                         float* reward, int R, int D, int Lr, int rows, int stop_id, int kind, hipStream_t st);
 void launch_beam_gather(const int* gidx, const int* latest, const float* c_src, const bf16* h_src,
                         const float* ctx_src, const float* a_src, const float* cov_src, const float* XGtab,
                         const float* Xtab, float* c_out, bf16* h_out, float* ctx_out, bf16* ctxb_out, float* cov_out,

@@ -113,6 +113,8 @@ def loader_workers(hps) -> int:
     ~0.7k examples/s under the GIL; the B = 256 step consumes ~12k/s."""
     if hps.mode != "train" or hps.inference or not hps.pad_enc_to_max or torch.cuda.device_count() == 0:
         return 0
+    if hps.rl_weight > 0:  # the self-critical trainer builds its 2n-row pack itself, after sampling
+        return 0
     if hps.loader_workers >= 0:
         return hps.loader_workers
     return max(1, min(8, (os.cpu_count() or 4) - 2))
@@ -147,7 +149,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                 batcher = loader
             else:
                 pad = hps.max_enc_steps if (torch.cuda.device_count() > 0 and hps.pad_enc_to_max) else None
-                batcher = Batcher(hps.data_path, vocab, hps, single_pass=hps.single_pass, seed=hps.seed,
+                # --rl_weight > 0: a step trains batch_size / 2 articles, each with its gold summary and a sample
+                bh = hps.replace(batch_size=hps.batch_size // 2) if hps.rl_weight > 0 else hps
+                batcher = Batcher(hps.data_path, vocab, bh, single_pass=hps.single_pass, seed=hps.seed,
                                   pad_enc_to=pad, rank=info.rank, world=info.world)
             from .train.loop import setup_training
             try:

@@ -80,6 +80,10 @@ class HParams:
     sampling_temp: float = 1.0     # top-k draws weigh a candidate by exp(log-prob / sampling_temp)
     n_samples: int = 1             # independent samples per article (1..16); the most probable one is the summary
     sample_seed: int = 0           # Philox key: the same seed gives the same samples whatever the batching
+    rl_weight: float = 0.0         # self-critical fine-tuning (train/scst.py): gamma in [0, 1] mixing the ML loss
+                                   # (1 - gamma) with the reward-weighted sample loss (gamma); 0 = ML training as before
+    rl_reward: str = "rouge_l"     # the reward of a sample against the gold summary: rouge_l | rouge_1 | rouge_2 |
+                                   # rouge_mean (the mean of the three F values)
     stream_max_wait_ms: float = 0.0   # streaming decode: queued requests always share a batch; after
                                       # the first, wait at most this long for more (0 = no waiting)
     save_model_secs: int = 60      # Supervisor(save_model_secs=60), run_summarization.py:199
@@ -217,6 +221,25 @@ def check_sampling(hps) -> None:
                          "built yet")
 
 
+RL_REWARDS = ("rouge_l", "rouge_1", "rouge_2", "rouge_mean")  # (the reward kernel's kind is the index)
+
+
+def check_scst(hps) -> None:
+    """The self-critical fine-tuning options (train/scst.py)."""
+    g = float(getattr(hps, "rl_weight", 0.0))
+    if not 0.0 <= g <= 1.0:
+        raise ValueError("rl_weight must be in [0, 1]")
+    if getattr(hps, "rl_reward", "rouge_l") not in RL_REWARDS:
+        raise ValueError(f"rl_reward must be one of {'/'.join(RL_REWARDS)}")
+    if g == 0:
+        return
+    if hps.batch_size % 2 or hps.batch_size < 2:
+        raise ValueError("rl_weight > 0 needs an even batch_size: a step trains batch_size / 2 articles, each "
+                         "with its gold summary and with one sample")
+    if not hps.pointer_gen:
+        raise ValueError("rl_weight > 0 needs pointer_gen=True")
+
+
 def check_hps(hps: HParams) -> None:
     if hps.mode not in ("train", "eval", "decode"):
         raise ValueError("The 'mode' flag must be one of train/eval/decode")
@@ -229,6 +252,7 @@ def check_hps(hps: HParams) -> None:
         raise ValueError("block_ngram_repeat must be >= 0 (0 or 1 = off)")
     check_penalties(hps)
     check_sampling(hps)
+    check_scst(hps)
 
 
 @dataclass

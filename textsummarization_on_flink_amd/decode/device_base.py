@@ -47,7 +47,7 @@ class DeviceDecoder:
     wide_switch = False  # (the beam decoder's ``wide_beam`` test switch)
 
     def __init__(self, hps, vocab, params, n_articles: int, T: int, use_graph: bool = True, chunk: int = 10,
-                 keep_attn: bool = True):
+                 keep_attn: bool = True, group_enc: int = None):
         width = int(getattr(hps, self._rows_flag))
         if width > self.MAX_BEAM:
             raise ValueError(f"{self._rows_flag} {width} exceeds {self.MAX_BEAM}, the largest beam the device "
@@ -75,7 +75,9 @@ class DeviceDecoder:
         # wait in that engine's buffers for their turn (TSAMD_DEC_GROUP_ENC, 1 = off): headline
         # decode 6273 -> 6792-6877, config #5 decode 2838-2855 (the side-stream overlap below)
         # -> 3154-3167 summaries/s (profiles/r6/decode_pair_encoder.md)
-        g = int(os.environ.get("TSAMD_DEC_GROUP_ENC", "8"))
+        # (``group_enc`` = 1: a caller that only ever decodes one batch at a time, train/scst.py, builds no
+        # group engine)
+        g = int(os.environ.get("TSAMD_DEC_GROUP_ENC", "8")) if group_enc is None else int(group_enc)
         self.group_enc = g if (g > 1 and self.dev.type == "cuda") else 1
         # without grouping: run batch n + 1's encoder on a side stream beside batch n's decode
         # steps when the encoder is long enough to pay for the CUs its persistent LSTM holds
@@ -158,14 +160,25 @@ class DeviceDecoder:
         self.b = b
         self._alloc_books()
 
-    def refresh_weights(self):
+    def refresh_weights(self, in_place: bool = False):
         """Per-token tables for the current weights (call after loading a checkpoint):
-        Xtab = emb . W_in[:E] + b_in  and  XGtab = Xtab . W_cell[:E] + b_cell."""
+        Xtab = emb . W_in[:E] + b_in  and  XGtab = Xtab . W_cell[:E] + b_cell.
+
+        ``in_place``: recompute them into the buffers they have (a trainer that samples from the weights it
+        updates every step, train/scst.py): the captured step graph reads those buffers and stays valid."""
         self.eng.pack()
         if getattr(self, "eng2", None) is not None:
             self.eng2.pack()
         p, E = self.p, self.eng.E
         emb = p[EMB]
+        if in_place and getattr(self, "Xtab", None) is not None:
+            torch.addmm(p[LIN_B], emb, p[LIN_M][:E], out=self.Xtab)
+            torch.addmm(p[CELL_B], self.Xtab, p[CELL_K][:E], out=self.XGtab)
+            if self.pg_w is not None:
+                self.pg_w.copy_(p[PG_M][:, 0])
+            if self.owT is not None:
+                self.owT.copy_(self.eng.pk["ow"].t())
+            return
         self.Xtab = (emb @ p[LIN_M][:E] + p[LIN_B]).contiguous()
         self.XGtab = (self.Xtab @ p[CELL_K][:E] + p[CELL_B]).contiguous()
         self.pg_w = p[PG_M][:, 0].contiguous() if self.hps.pointer_gen else None

@@ -32,13 +32,14 @@ class DeviceSampler(DeviceDecoder):
     _fused_tail = False  # the draw is the tail of the unfused step
 
     def __init__(self, hps, vocab, params, n_articles: int, T: int, use_graph: bool = True, chunk: int = 10,
-                 keep_attn: bool = True):
+                 keep_attn: bool = True, group_enc: int = None):
         check_sampling(hps)
         if not sampling_on(hps):
             raise ValueError("DeviceSampler needs sampling_topk >= 0 (DeviceBeamDecoder runs beam search)")
         self.topk, self.n_samples = int(hps.sampling_topk), int(hps.n_samples)
         self.articles_seen = 0  # decode / decode_batches: sample_base = n_samples * articles decoded so far
-        super().__init__(hps, vocab, params, n_articles, T, use_graph=use_graph, chunk=chunk, keep_attn=keep_attn)
+        super().__init__(hps, vocab, params, n_articles, T, use_graph=use_graph, chunk=chunk, keep_attn=keep_attn,
+                         group_enc=group_enc)
 
     # ------------------------------------------------------------------ the plan
     def _candidates(self) -> int:

@@ -10,7 +10,9 @@ import torch
 F32 = torch.float32
 
 
-def host_inputs(batch, hps, D: int, sort_rows: bool = False, need_grad: bool = True) -> Dict[str, np.ndarray]:
+def host_inputs(batch, hps, D: int, sort_rows: bool = False, need_grad: bool = True,
+                row_scale: Optional[np.ndarray] = None, cov_scale: Optional[np.ndarray] = None
+                ) -> Dict[str, np.ndarray]:
     """The engine's per-batch inputs as host arrays (pure numpy: runs in loader worker
     processes too): token ids, lengths, the reversed-index map of the backward LSTM
     direction, extended-vocab ids, step-major decoder inputs / targets and the per-(step,
@@ -22,7 +24,12 @@ def host_inputs(batch, hps, D: int, sort_rows: bool = False, need_grad: bool = T
     sum over rows; ``row_src[b]`` is the batch row of engine row b.
 
     ``need_grad`` False (decode / eval packs): the embedding-gradient id order is not computed
-    (zeros; no backward reads it) -- the largest host cost of a serving batch."""
+    (zeros; no backward reads it) -- the largest host cost of a serving batch.
+
+    ``row_scale`` / ``cov_scale`` ([B] floats, batch row order; None = 1): per-row multipliers of the
+    loss weights ``rowg`` and of the coverage-loss weights ``gcl``, applied after the normalisation
+    above and before the row sort (train/scst.py weighs sample rows by their advantage with them; a
+    weight may be negative).  A row whose weights are all 0 is skipped like a padded row."""
     T = batch.enc_batch.shape[1]
     lens = batch.enc_lens.astype(np.int64)
     if lens.min() < 1:
@@ -41,6 +48,10 @@ def host_inputs(batch, hps, D: int, sort_rows: bool = False, need_grad: bool = T
         wm = dm * valid[:, None]
         rowg = wm / wm.sum()
     gcl = hps.cov_loss_wt * dm * (valid / (np.maximum(dec_lens, 1) * nvalid))[:, None]
+    if row_scale is not None:
+        rowg = rowg * _row_scale(row_scale, len(valid), "row_scale")[:, None]
+    if cov_scale is not None:
+        gcl = gcl * _row_scale(cov_scale, len(valid), "cov_scale")[:, None]
     # live decoder steps per row: 1 + the last step with a nonzero loss weight (0: none).  Steps
     # past it reach only masked loss terms (model.py:252-268), so their forward values and
     # gradients need not be computed (EngineConfig.skip_pad_steps)
@@ -80,6 +91,13 @@ def host_inputs(batch, hps, D: int, sort_rows: bool = False, need_grad: bool = T
         "vblk": vblk,
         "vblk_n": np.array([len(live_ids)], dtype=np.int32),
     }
+
+
+def _row_scale(x, B: int, name: str) -> np.ndarray:
+    x = np.asarray(x, dtype=np.float64)
+    if x.shape != (B,) or not np.isfinite(x).all():
+        raise ValueError(f"{name}: {B} finite per-row multipliers expected")
+    return x
 
 
 def emb_sort(enc_batch: np.ndarray, dec_t: np.ndarray):

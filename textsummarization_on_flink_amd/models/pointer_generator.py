@@ -551,10 +551,11 @@ class HipPointerGenerator:
         self.f32 = f32
 
     # ------------------------------------------------------------------ inputs
-    def set_batch(self, batch) -> None:
+    def set_batch(self, batch, row_scale=None, cov_scale=None) -> None:
         """Host batch -> static device buffers: one H2D copy of a pinned pack.  A batch from
         the multi-process loader (data/loader.py) arrives with ``host_pack`` already built
-        by a worker process; otherwise it is built here."""
+        by a worker process; otherwise it is built here.  ``row_scale`` / ``cov_scale``: the per-row
+        multipliers of ``host_inputs`` (not with a prebuilt pack: its weights are already final)."""
         B, T = self.B, self.T
         if batch.enc_batch.shape != (B, T):
             raise ValueError(f"batch enc shape {batch.enc_batch.shape} != engine shape {(B, T)}")
@@ -564,12 +565,15 @@ class HipPointerGenerator:
             self._in_ev[i].synchronize()  # the copy out of this pack (two batches ago) is done
         hn = self._in_host[i].numpy()
         if packed is not None:
+            if row_scale is not None or cov_scale is not None:
+                raise ValueError("row_scale / cov_scale cannot be applied to a batch with a prebuilt host_pack")
             if len(packed) != hn.nbytes:
                 raise ValueError(f"host pack of {len(packed)} bytes, engine expects {hn.nbytes}")
             hn[:] = np.frombuffer(packed, dtype=np.uint8)
         else:
             pack_host_inputs(host_inputs(batch, self.hps, self.D, sort_rows=self.skip_pad,
-                                         need_grad=getattr(self.hps, "mode", "train") != "decode"), self._in_layout, hn)
+                                         need_grad=getattr(self.hps, "mode", "train") != "decode",
+                                         row_scale=row_scale, cov_scale=cov_scale), self._in_layout, hn)
         if self.compact_vocab:  # this batch's live vocab-head blocks -> the head's block-count bucket
             o = self._in_off["vblk_n"]
             nlive = int(np.frombuffer(hn, dtype=np.int32, count=1, offset=o)[0])

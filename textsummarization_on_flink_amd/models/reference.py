@@ -132,8 +132,13 @@ class ReferencePointerGenerator:
         return ext.scatter_add(1, ext_ids.long(), (1 - p_gen[:, None]) * attn)
 
     # ------------------------------------------------------------------ train / eval
-    def forward(self, W, batch: Dict[str, torch.Tensor]):
-        """Returns dict(loss, coverage_loss, total_loss, attn_dists [D,B,T], p_gens [D,B])."""
+    def forward(self, W, batch: Dict[str, torch.Tensor], row_scale: Optional[torch.Tensor] = None,
+                cov_scale: Optional[torch.Tensor] = None):
+        """Returns dict(loss, coverage_loss, total_loss, attn_dists [D,B,T], p_gens [D,B]).
+
+        ``row_scale`` / ``cov_scale`` ([B], constants): per-row multipliers of the loss and of the coverage
+        loss, loss = sum_b scale_b * per_ex_b / sum(valid) (the weighted objective of train/scst.py;
+        ``models.host_inputs.host_inputs`` takes the same two).  None leaves the loss as it is."""
         hps = self.hps
         enc_batch, lens = batch["enc_batch"], batch["enc_lens"]
         mask_enc = batch["enc_padding_mask"]
@@ -169,15 +174,16 @@ class ReferencePointerGenerator:
                 fd = self.final_dist(vocab_dist[t], attn[t], pg[t], ext, max_oovs)
                 gold = fd.gather(1, target[t][:, None].long())[:, 0]
                 losses.append(-torch.log(gold))
-            loss = mask_and_avg(torch.stack(losses, 0), dec_mask, valid)
+            loss = mask_and_avg(torch.stack(losses, 0), dec_mask, valid, row_scale)
         else:
             pg = None
             ce = Fn.cross_entropy(logits.reshape(D * B, -1), target.reshape(-1).long(), reduction="none").view(D, B)
             w = dec_mask.t() * valid[None, :]
-            loss = (ce * w).sum() / w.sum()  # tf.contrib.seq2seq.sequence_loss
+            ws = w if row_scale is None else w * row_scale.to(w.dtype)[None, :]
+            loss = (ce * ws).sum() / w.sum()  # tf.contrib.seq2seq.sequence_loss
         out = {"loss": loss, "attn_dists": attn, "p_gens": pg}
         if hps.coverage:
-            covl = coverage_loss(attn, dec_mask, valid)
+            covl = coverage_loss(attn, dec_mask, valid, cov_scale)
             out["coverage_loss"] = covl
             out["total_loss"] = loss + hps.cov_loss_wt * covl
         else:
@@ -213,21 +219,24 @@ class ReferencePointerGenerator:
         return vd, c, h, a, p_gen, cov
 
 
-def mask_and_avg(values, dec_mask, valid):
-    """values [D,B]; per-example masked mean over dec_len, then mean over (valid) batch."""
+def mask_and_avg(values, dec_mask, valid, scale=None):
+    """values [D,B]; per-example masked mean over dec_len, then mean over (valid) batch; ``scale`` [B]
+    multiplies each example's mean (the mean stays over the valid rows)."""
     dec_lens = dec_mask.sum(1)
     per_ex = (values * dec_mask.t()).sum(0) / dec_lens
+    if scale is not None:
+        per_ex = per_ex * scale.to(per_ex.dtype)
     return (per_ex * valid).sum() / valid.sum()
 
 
-def coverage_loss(attn, dec_mask, valid):
+def coverage_loss(attn, dec_mask, valid, scale=None):
     """sum_i min(a_t, cov_t) with cov starting at zero (model.py:463-480)."""
     cov = torch.zeros_like(attn[0])
     losses = []
     for t in range(attn.shape[0]):
         losses.append(torch.minimum(attn[t], cov).sum(1))
         cov = cov + attn[t]
-    return mask_and_avg(torch.stack(losses, 0), dec_mask, valid)
+    return mask_and_avg(torch.stack(losses, 0), dec_mask, valid, scale)
 
 
 def batch_to_tensors(batch, device="cpu") -> Dict[str, torch.Tensor]:

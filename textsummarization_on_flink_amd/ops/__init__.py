@@ -22,7 +22,8 @@ _LIB = os.path.join(_PKG, os.environ.get("TSAMD_C_LIB") or ("_C_debug.so" if DEB
 DEBUG_CHECKS = {1: "to_step_frame row id", 2: "step-frame reversal index", 3: "embedding-gradient token id",
                 4: "attention encoder length", 5: "pointer-loss / copy-mass encoder length",
                 6: "beam parent row", 7: "beam latest token", 8: "n-gram blocking token-sequence index",
-                9: "wide beam candidate rank / slot", 10: "full-distribution draw chunk"}
+                9: "wide beam candidate rank / slot", 10: "full-distribution draw chunk",
+                11: "rouge_reward sample length", 12: "rouge_reward reference length"}
 _lock = threading.Lock()
 _loaded = False
 

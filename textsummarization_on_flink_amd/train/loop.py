@@ -78,9 +78,17 @@ class MetricsLogger:
             self._tb = None
 
 
-def make_trainer(hps, vsize: int, info: Optional[DistInfo] = None, device: Optional[str] = None, params=None):
-    """GPU: hipGraph HIP-kernel trainer (static shapes B x max_enc_steps).  CPU: oracle."""
+def make_trainer(hps, vsize: int, info: Optional[DistInfo] = None, device: Optional[str] = None, params=None,
+                 vocab=None):
+    """GPU: hipGraph HIP-kernel trainer (static shapes B x max_enc_steps).  CPU: oracle.
+    ``--rl_weight`` > 0 (training only): the self-critical ``train.scst.ScstTrainer`` around the GPU trainer;
+    it needs ``vocab`` and takes batches of batch_size / 2 articles."""
     use_gpu = (device or ("cuda" if torch.cuda.is_available() else "cpu")).startswith("cuda")
+    if getattr(hps, "rl_weight", 0.0) > 0 and hps.mode == "train":
+        from .scst import ScstTrainer
+        if vocab is None:
+            raise ValueError("rl_weight > 0: make_trainer needs the vocabulary")
+        return ScstTrainer(hps, vocab, device="cuda" if use_gpu else "cpu", info=info, params=params)
     if use_gpu:
         from .trainer import GraphTrainer
         return GraphTrainer(hps, vsize, B=hps.batch_size, T=hps.max_enc_steps, info=info, params=params,
@@ -182,7 +190,7 @@ def setup_training(hps, vocab, batcher, info: Optional[DistInfo] = None, metrics
     info = info or DistInfo()
     train_dir = os.path.join(hps.log_root, "train")
     os.makedirs(train_dir, exist_ok=True)
-    trainer = make_trainer(hps, vocab.size(), info=info, device=device)
+    trainer = make_trainer(hps, vocab.size(), info=info, device=device, vocab=vocab)
     if hps.convert_to_coverage_model:
         if not hps.coverage:
             raise ValueError("To convert your non-coverage model to a coverage model, run with "
@@ -197,6 +205,8 @@ def setup_training(hps, vocab, batcher, info: Optional[DistInfo] = None, metrics
         trainer.global_step = ckpt.restore(latest, trainer.params, load_adagrad=True)
         if hasattr(trainer, "engine"):
             trainer.engine.pack()
+        if hasattr(trainer, "refresh_samplers"):
+            trainer.refresh_samplers()
         log.info("Restored %s at step %d", latest, trainer.global_step)
     if info.enabled:
         # resume on every rank from the chief's state

@@ -244,8 +244,10 @@ class GraphTrainer:
         torch.cuda.synchronize()
 
     # ------------------------------------------------------------------ step
-    def step(self, batch) -> Dict[str, torch.Tensor]:
-        self.engine.set_batch(batch)
+    def step(self, batch, row_scale=None, cov_scale=None) -> Dict[str, torch.Tensor]:
+        """One training step.  ``row_scale`` / ``cov_scale``: per-row multipliers of the loss and coverage-loss
+        weights (``models.host_inputs.host_inputs``); inputs of the captured graphs, so no recapture."""
+        self.engine.set_batch(batch, row_scale=row_scale, cov_scale=cov_scale)
         if self.use_graph:
             if self.g_fb is None:
                 self.capture()
